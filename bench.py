@@ -19,8 +19,15 @@ src/poseidon/mod.rs:95-118) over one device-resident batch of synthetic random s
   --workload c3 / h3 / h9   wide states (BN254 Fr, t=9, 2^18 per GPU) and the absorb/squeeze hash driver.
 
 Rank 0 prints ONE JSON line.  `value` = permutations per second over all ranks, inputs already in HBM.
-`roofline` prices the dominant kernel against HBM (algorithmic 2*t*32 bytes per permutation); `int_valu` against
-the v_mad_u64_u32 issue rate measured on this device in this run (pmx_diag_int_valu_peak), which is what binds it;
+`roofline` prices the dominant kernel against HBM (algorithmic 2*t*32 bytes per permutation).
+
+A plain run sets up, spins the device up, runs the W warmup and the K timed steps and prints the line: the figures below
+that take work of their own are null in it.  --full adds them: `int_valu`, `valu_issue` and `clock_normalised` (in-run
+calibrations on the device before the warm-up), `verified` (a check against the C restatement) and, at N = 1, `cpu_baseline`.
+--dump-outputs DIR writes what the K-th step computed (rank 0's view) as DIR/<name>.npy; see dump_outputs().
+
+With --full, `int_valu` prices the dominant kernel against the v_mad_u64_u32 issue rate measured on this device in this run
+(pmx_diag_int_valu_peak), which is what binds it;
 `engine` is what the library's launchers dispatch for this call (pmx_ctx_engine_info) and feeds the multiply count;
 `valu_issue` prices the kernel's VALU instruction count against the issue slot measured in this run (pmx_diag_issue_slot);
 `cpu_baseline` times the C restatement of the reference algorithm (oracle/, kind "port") on the host cores for a
@@ -132,10 +139,18 @@ def parse_args():
     ap.add_argument("--single-process", action="store_true",
                     help="N>1 without a launcher: ONE process drives all N GPUs through the C ABI's single-process device group "
                          "(pmx_mgpu_create = ncclCommInitAll; what a Rust caller uses) instead of starting one rank per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take work of their own: in-run VALU calibrations (int_valu, valu_issue, clock_normalised), "
+                         "the check against the C restatement (verified) and, at N = 1, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the check against the C restatement")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the all-cores cpu_baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the K-th step computed as DIR/<name>.npy (float32 / float64, a fixed sample)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -202,6 +217,33 @@ def sample_indices(n, k):
                                      np.linspace(0, n - 1, k // 2).astype(np.int64)]))
 
 
+DUMP_ROWS = 16384           # rows --dump-outputs keeps of a larger output: a fixed seeded sample
+DUMP_LIMIT = 64 << 20       # bytes of array data one dump may write in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the K-th step left (torch tensors, name -> [rows, ...]) as out_dir/<name>.npy, so that two builds
+    can be compared output for output.  A field element ([..., 4] int64 limbs) is written as its 32 little-endian bytes, each a
+    float32 in 0 .. 255: exact, and a changed bit moves some value by at least 1.  Mode words (int32) are written as float64.  An
+    array of more than DUMP_ROWS rows keeps the rows of a fixed seeded sample, the same in every run of the same size; their
+    indices go to out_dir/<name>_rows.npy."""
+    import torch
+    files = {}
+    for name, x in arrays.items():
+        if x.shape[0] > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(0x5EEDD0).choice(x.shape[0], DUMP_ROWS, replace=False))
+            x = x[torch.from_numpy(idx).to(x.device)]
+            files[name + "_rows"] = idx.astype(np.float64)
+        a = np.ascontiguousarray(x.cpu().numpy())
+        files[name] = a.view(np.uint8).astype(np.float32) if a.dtype == np.int64 else a.astype(np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes, above the limit of %d" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` with no launcher environment: start the N ranks OURSELVES, as a child process
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` - the very command the
@@ -247,6 +289,8 @@ def main_single_process(args):
         raise SystemExit("bench.py needs an MI355X: the Poseidon path has no CPU fallback")
     if args.workload in HASH_SHAPES or args.workload in DUPLEX_SHAPES:
         raise SystemExit("--single-process runs the permutation batches (c2, c3, k3, w*) and the sharded tree (c5)")
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs is written by the one-rank-per-GPU form: drop --single-process")
     visible = torch.cuda.device_count()
     if rehearsal:
         devices = [l % visible for l in range(world)]
@@ -274,8 +318,10 @@ def main_single_process(args):
     field = S.FIELDS[field_name]
     cfg = S.poseidon_config_from_lfsr(field, rate, alpha, rf, rp)
 
-    peak = _lib.PmxValuPeak()
-    _lib.check_diag(_lib.diag_lib().pmx_diag_int_valu_peak(devices[0], 0.1, peak))
+    peak = None
+    if args.full:
+        peak = _lib.PmxValuPeak()
+        _lib.check_diag(_lib.diag_lib().pmx_diag_int_valu_peak(devices[0], 0.1, peak))
     group = mgpu.DeviceGroup.single_process(cfg, devices=devices)
     info = group.info()
     rccl = {"ranks": info["comm_ranks"], "version": info["rccl_version_str"], "rank0_is": info["comm_first_rank"],
@@ -286,11 +332,12 @@ def main_single_process(args):
     spans = [group.local_span(n_total, l) for l in range(world)]
     n = spans[0][1]
     slot = {}
-    early = _lib.PmxEngineInfo()
-    _lib.check(_lib.lib().pmx_ctx_engine_info(ctx._h, _lib.OP_COMPRESS if merkle else _lib.OP_PERMUTE, (n // 2 if merkle else n), 0, early))
-    r = _lib.PmxIssueSlot()
-    _lib.check_diag(_lib.diag_lib().pmx_diag_issue_slot(devices[0], max(1, min(8, early.waves_per_simd)), 0.06, r))
-    slot[max(1, min(8, early.waves_per_simd))] = r
+    if args.full:
+        early = _lib.PmxEngineInfo()
+        _lib.check(_lib.lib().pmx_ctx_engine_info(ctx._h, _lib.OP_COMPRESS if merkle else _lib.OP_PERMUTE, (n // 2 if merkle else n), 0, early))
+        r = _lib.PmxIssueSlot()
+        _lib.check_diag(_lib.diag_lib().pmx_diag_issue_slot(devices[0], max(1, min(8, early.waves_per_simd)), 0.06, r))
+        slot[max(1, min(8, early.waves_per_simd))] = r
     devs = [torch.device("cuda", d) for d in devices]
     streams = [torch.cuda.ExternalStream(group.stream(l), device=devs[l]) for l in range(world)]
 
@@ -384,7 +431,7 @@ def main_single_process(args):
     steps_s = max(a.elapsed_time(b) for a, b in zip(ev0, ev_k)) / 1e3
 
     verify = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         cr = oracle_engine(field_name, rate, alpha, rf, rp)
         verify = {"ok": True, "engine": "oracle/poseidon_ref.c (C restatement)", "what": None}
         b = make_buffers()
@@ -523,9 +570,11 @@ def main():
     field = S.FIELDS[field_name]
     cfg = S.poseidon_config_from_lfsr(field, rate, alpha, rf, rp)
 
-    # ---- per-run integer-VALU roofline of THIS device, before anything is timed -----------------------------------------
-    peak = _lib.PmxValuPeak()
-    _lib.check_diag(_lib.diag_lib().pmx_diag_int_valu_peak(local_rank, 0.1, peak))
+    # ---- (--full) per-run integer-VALU roofline of THIS device, before anything is timed ---------------------------------
+    peak = None
+    if args.full:
+        peak = _lib.PmxValuPeak()
+        _lib.check_diag(_lib.diag_lib().pmx_diag_int_valu_peak(local_rank, 0.1, peak))
     slot = {}          # waves per SIMD -> in-run issue-slot measurement (pmx_diag_issue_slot), filled for the kernel's occupancy below
 
     def issue_slot(waves):
@@ -562,7 +611,7 @@ def main():
             dist.destroy_process_group()
             sys.exit(4)
     ctx = cfg.context(local_rank)
-    if rank == 0:       # the issue slot at the dominant kernel's occupancy, measured before anything is timed
+    if rank == 0 and args.full:       # the issue slot at the dominant kernel's occupancy, measured before anything is timed
         early = _lib.PmxEngineInfo()
         _lib.check(_lib.lib().pmx_ctx_engine_info(ctx._h, _lib.OP_COMPRESS if args.workload == "c5" else (_lib.OP_HASH if args.workload in HASH_SHAPES else
                                                   (_lib.OP_ABSORB if args.workload in DUPLEX_SHAPES else _lib.OP_PERMUTE)),
@@ -598,6 +647,13 @@ def main():
 
         def final_gather():
             pass
+
+        def reset():
+            for x in (d_st, d_tag, d_idx):
+                x.zero_()
+
+        def outputs():
+            return {"squeezed": d_out, "sponge_states": d_st, "sponge_modes": d_tag, "sponge_indices": d_idx}
     elif hashing:
         in_len, out_len, perms_per_row = HASH_SHAPES[args.workload]
         host_in, d_in = fresh_inputs()
@@ -609,6 +665,12 @@ def main():
 
         def final_gather():
             pass
+
+        def reset():
+            pass
+
+        def outputs():
+            return {"digests": d_out}
     elif merkle:
         # leaves of this rank's subtree, resident in the first n rows of the node array [2n-1][4]
         host_in, d_leaves = fresh_inputs()
@@ -625,6 +687,12 @@ def main():
 
         def final_gather():
             pass
+
+        def reset():
+            pass
+
+        def outputs():
+            return {"nodes": nodes, "root": top[-1:] if group is not None else nodes[-1:]}
     else:
         host_in, buf = fresh_inputs()
         buf = buf.reshape(n, t, 4)
@@ -654,6 +722,12 @@ def main():
             if world > 1 and args.gather in ("final", "root"):
                 gather_now(buf)
 
+        def reset():                             # the steps permute in place: back to the seeded batch
+            buf.copy_(torch.from_numpy(host_in.view(np.int64)).reshape(n, t, 4))
+
+        def outputs():
+            return {"states": gathered if gathered is not None else buf}
+
     def barrier():
         torch.cuda.synchronize()
         if world > 1:
@@ -672,6 +746,10 @@ def main():
         i_spin += 1
         if i_spin % 4 == 0:
             torch.cuda.synchronize()
+    # the spin-up runs as many steps as fit its time: undo them, so that the W + K steps start from the seeded inputs in every run
+    torch.cuda.synchronize()
+    reset()
+    torch.cuda.synchronize()
     for i in range(args.warmup):
         step(i)
     final_gather()      # also warms RCCL's lazily built rings up, outside the timed region
@@ -700,10 +778,12 @@ def main():
     if world > 1:
         dist.all_reduce(times, op=dist.ReduceOp.MAX)
     elapsed, dev_s, steps_s = float(times[0]), float(times[1]), float(times[2])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())
 
-    # ---- verification (untimed): one pass over a FRESH copy of the seeded inputs, sample against the C restatement ------
+    # ---- (--full) verification (untimed): one pass over a FRESH copy of the seeded inputs, sample against the C restatement
     verify = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verify = run_verification(locals())
         flag = torch.tensor([1 if verify["ok"] else 0], device=ctl)
         if world > 1:
@@ -715,7 +795,7 @@ def main():
                           steps_s=steps_s, dev_s=dev_s, scaling=scaling, baseline_cfg=baseline_cfg, rccl=rccl, verify=verify, rehearsal=rehearsal,
                           in_len=(in_len if (hashing or duplex) else 0), out_len=(out_len if (hashing or duplex) else 0),
                           perms_per_row=(perms_per_row if (hashing or duplex) else 1))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(field_name, rate, alpha, rf, rp, seed, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
@@ -770,9 +850,11 @@ def result_line(args, ctx, peak, slot, *, world, n, n_total, units_per_step, ela
         mads -= (t - out_len) * last_row / perms_per_row
     mad_rate = mads * per_gpu_units / kernel_s
     traffic, traffic_src = load_traffic(args.workload, per_gpu_units)
-    valu_issue = load_valu_issue(args.workload, per_gpu_units, kernel_s, peak.compute_units, mads, info, slot)
-    if mfma_dense and not (merkle or hashing or duplex):
-        price_products(valu_issue, matrix_products_per_permutation(t, rf, rp, int(info.partial_window), int(info.row_tables) == 2), peak.shader_clock_hz)
+    valu_issue = None           # (without --full there is no in-run calibration: peak is None)
+    if peak is not None:
+        valu_issue = load_valu_issue(args.workload, per_gpu_units, kernel_s, peak.compute_units, mads, info, slot)
+        if mfma_dense and not (merkle or hashing or duplex):
+            price_products(valu_issue, matrix_products_per_permutation(t, rf, rp, int(info.partial_window), int(info.row_tables) == 2), peak.shader_clock_hz)
     out = {
         "metric": "Poseidon permutations/sec (%s, t=%d)" % ({"bls12_381_fr": "BLS12-381 Fr", "bn254_fr": "BN254 Fr"}[field_name], t),
         "value": value, "unit": "permutations/s",
@@ -800,7 +882,7 @@ def result_line(args, ctx, peak, slot, *, world, n, n_total, units_per_step, ela
                                ("pmx::hash_kernel" if hashing else ("the driver's kernels: " + info.engine.decode() if duplex else "pmx::permute_kernel")),
                      "kernel_ms": 1e3 * kernel_s, "algorithmic_bytes_per_launch": algo_bytes,
                      "note": "integer-VALU bound, not HBM bound (DESIGN.md): see int_valu"},
-        "int_valu": {"bound": "v_mad_u64_u32 issue", "achieved": mad_rate, "peak": peak.lane_mads_per_s,
+        "int_valu": None if peak is None else {"bound": "v_mad_u64_u32 issue", "achieved": mad_rate, "peak": peak.lane_mads_per_s,
                      "unit": "lane-instr/s", "frac": mad_rate / peak.lane_mads_per_s, "mads_per_permutation": mads,
                      "dense_layers": "v_mfma_i32_32x32x32_i8 (pmx_mfma.hpp): not counted as multiplies" if mfma_dense else "VALU",
                      "model_note": ("an UPPER bound of the multiplies a permutation executes: pmx_ctx_engine_info does not say which t = 3 windows take their history "
@@ -816,7 +898,7 @@ def result_line(args, ctx, peak, slot, *, world, n, n_total, units_per_step, ela
         # the same run in units that do not move with the clock a box happens to hold (boxes of this pool hold 2.11 ... 2.25 GHz under this load):
         # shader clocks one SIMD spends per permutation, and - where the instruction count is known - clocks per VALU instruction and SIMD
         # (the issue slot is 4: one wave instruction per 16 lanes x 4 passes)
-        "clock_normalised": clock_normalised(kernel_s, peak.shader_clock_hz, peak.compute_units, units_per_step / max(world, 1), valu_issue),
+        "clock_normalised": None if peak is None else clock_normalised(kernel_s, peak.shader_clock_hz, peak.compute_units, units_per_step / max(world, 1), valu_issue),
         # (overlap forms: the transfers run inside the K-th step - there is no epilogue to time; compare ms_per_step x steps with --gather none)
         "gather_ms": 1e3 * (dev_s - steps_s) if (world > 1 and args.gather not in ("overlap", "overlap-root")) else None,
         "gather_inside_last_step": (world > 1 and args.gather in ("overlap", "overlap-root") and not (merkle or hashing or duplex)) or None,

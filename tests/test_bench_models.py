@@ -64,3 +64,48 @@ def test_gather_predictions(gather, chunks):
     else:
         assert abs(ms - one) < 1e-9 and (("ncclSend" in text) == (gather == "root"))
     assert bench.gather_model(args, 1, n, t, False) == (None, None) and bench.gather_model(args, world, n, t, True) == (None, None)
+
+
+def test_dump_outputs_is_exact_sampled_and_bounded(tmp_path):
+    """--dump-outputs: limbs as their bytes in float32 (exact), mode words as float64, larger arrays as the same seeded row sample in
+    every run, and the whole dump under 64 MB even for the widest driver workload (d9: 2^18 sponges of t = 9, squeeze(9))."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(7)
+    small = rng.integers(0, 1 << 63, size=(100, 3, 4), dtype=np.int64)
+    big = rng.integers(0, 1 << 63, size=(bench.DUMP_ROWS + 5, 9, 4), dtype=np.int64)
+    modes = np.arange(bench.DUMP_ROWS + 5, dtype=np.int32)
+    arrays = {"small": torch.from_numpy(small), "big": torch.from_numpy(big), "modes": torch.from_numpy(modes)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["big.npy", "big_rows.npy", "modes.npy", "modes_rows.npy", "small.npy"]
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.shape == (100, 3, 32) and np.array_equal(got.astype(np.uint8).view(np.int64), small)
+    rows = np.load(tmp_path / "a" / "big_rows.npy").astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy").astype(np.uint8).view(np.int64), big[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "modes.npy"), modes[rows].astype(np.float64))
+    # the largest dump of any workload at its default size stays under the limit
+    d9_bytes = 2 * bench.DUMP_ROWS * 9 * 32 * 4 + 2 * bench.DUMP_ROWS * 8 + 4 * bench.DUMP_ROWS * 8
+    assert d9_bytes <= bench.DUMP_LIMIT
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"]])
+def test_steps_below_one_are_refused(argv, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.parse_args()
+    assert e.value.code == 2
+
+
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "out"

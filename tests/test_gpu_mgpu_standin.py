@@ -169,7 +169,7 @@ def test_bench_multi_rank_path_runs_through_the_device_group(world, extra, tmp_p
     port = 29500 + (os.getpid() * 7 + world) % 400
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--spinup-seconds", "0.05"] + extra, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+                        "--full", "--no-cpu-baseline", "--spinup-seconds", "0.05"] + extra, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     text = p.stdout.decode(errors="replace")
     lines = [json.loads(l) for l in text.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, text[-3000:]
@@ -201,7 +201,7 @@ def test_bench_gpus_n_needs_no_launcher(world, form, extra, tmp_path):
         env.pop("FAKE_RCCL_XPROC")                     # the slots are threads of one process here
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--spinup-seconds", "0.05"] + extra
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--full", "--spinup-seconds", "0.05"] + extra
     if form == "single":
         cmd.append("--single-process")
     p = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05f; mkdir -p $O
 cp tools/ab/libposeidon_new.so sponge_amd/libposeidon_mi355x.so    # (the build with the slimmer row finish)
 for l in 15 16 17 18 19 20; do
-  python bench.py --workload c3 --total-log2 $l --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('c3 2^$l states: %.4g perm/s  kernel_ms %.4f  clk %.3g'%(d['value'],d['roofline']['kernel_ms'],d['int_valu']['shader_clock_hz']))"
+  python bench.py --full --workload c3 --total-log2 $l --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('c3 2^$l states: %.4g perm/s  kernel_ms %.4f  clk %.3g'%(d['value'],d['roofline']['kernel_ms'],d['int_valu']['shader_clock_hz']))"
 done 2>&1 | tee $O/c3_by_batch_size.txt
 for l in 17 18 19 20 21; do
   python bench.py --workload c2 --total-log2 $l --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('c2 2^$l states: %.4g perm/s  kernel_ms %.4f'%(d['value'],d['roofline']['kernel_ms']))"

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06a; mkdir -p $O
 ./tools/hwid_probe 2048 3000 > $O/hwid_probe.txt 2>&1; head -12 $O/hwid_probe.txt; tail -4 $O/hwid_probe.txt
 run() {  # workload, stagger
-  PMX_STAGGER=$2 python bench.py --workload $1 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$1 stagger=$2 %.4g perm/s  kernel_ms %.4f verified %s clk %.3g'%(d['value'],d['roofline']['kernel_ms'],d['verified'],d['int_valu']['shader_clock_hz']))"
+  PMX_STAGGER=$2 python bench.py --full --workload $1 --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$1 stagger=$2 %.4g perm/s  kernel_ms %.4f verified %s clk %.3g'%(d['value'],d['roofline']['kernel_ms'],d['verified'],d['int_valu']['shader_clock_hz']))"
 }
 for round in 1 2; do
   for st in 0 2,0 4,0 6,0 8,0 12,0 4,1 8,1 4,2 8,2 4,3 8,3; do run c3 $st; done

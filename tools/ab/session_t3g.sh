@@ -7,8 +7,8 @@ rocm-smi --showproductname 2>/dev/null | head -8 > $O/device.txt
 ( timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "golden or traces or merkle_trees or consistency" ) > $O/pytest_parity.log 2>&1; tail -3 $O/pytest_parity.log
 WORKLOADS="k3 c2" STEPS=20 bash tools/ab/ab.sh 2>&1 | tee $O/ab_t3_every_exponent.txt
 cp tools/ab/libposeidon_new.so sponge_amd/libposeidon_mi355x.so
-timeout 600 python bench.py --workload k3 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_k3.json 2> $O/bench_k3.err
-timeout 600 python bench.py --workload c3 --steps 8 --warmup 2 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err
+timeout 600 python bench.py --full --workload k3 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_k3.json 2> $O/bench_k3.err
+timeout 600 python bench.py --full --workload c3 --steps 8 --warmup 2 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err
 python - <<'PY'
 import json
 for w in ("k3","c3"):

@@ -30,14 +30,14 @@ for n in 1 2 4 8; do
   [ "$n" -le "$MAX" ] || break
   for w in c2 c5; do
     steps=20; [ "$w" = c5 ] && steps=5
-    timeout 1800 $PY bench.py --gpus $n --steps $steps --warmup 5 --workload $w --no-cpu-baseline > "$OUT/${w}_n${n}_ranks.json" 2> "$OUT/${w}_n${n}_ranks.err"
+    timeout 1800 $PY bench.py --full --gpus $n --steps $steps --warmup 5 --workload $w --no-cpu-baseline > "$OUT/${w}_n${n}_ranks.json" 2> "$OUT/${w}_n${n}_ranks.err"
     echo "rc $? ${w} N=$n ranks" >> "$OUT/rc.txt"
     if [ "$n" -gt 1 ]; then
-      timeout 1800 $PY bench.py --gpus $n --single-process --steps $steps --warmup 5 --workload $w > "$OUT/${w}_n${n}_single.json" 2> "$OUT/${w}_n${n}_single.err"
+      timeout 1800 $PY bench.py --full --gpus $n --single-process --steps $steps --warmup 5 --workload $w > "$OUT/${w}_n${n}_single.json" 2> "$OUT/${w}_n${n}_single.err"
       echo "rc $? ${w} N=$n single" >> "$OUT/rc.txt"
       if [ "$w" = c2 ]; then   # the other forms of the epilogue: to rank 0 only, and piece by piece behind the last step's kernels
         for g in root overlap overlap-root; do
-          timeout 1800 $PY bench.py --gpus $n --steps $steps --warmup 5 --workload c2 --gather $g --no-cpu-baseline > "$OUT/c2_n${n}_ranks_${g}.json" 2> "$OUT/c2_n${n}_ranks_${g}.err"
+          timeout 1800 $PY bench.py --full --gpus $n --steps $steps --warmup 5 --workload c2 --gather $g --no-cpu-baseline > "$OUT/c2_n${n}_ranks_${g}.json" 2> "$OUT/c2_n${n}_ranks_${g}.err"
           echo "rc $? c2 N=$n ranks --gather $g" >> "$OUT/rc.txt"
         done
       fi

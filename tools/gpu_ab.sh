@@ -17,7 +17,7 @@ for w in $WL; do
     *) args="--workload $w --steps 8 --warmup 2";;
   esac
   for rep in 1 2; do
-    timeout 600 python bench.py $args --no-cpu-baseline > $OUT/bench_${w}_$rep.json 2> $OUT/bench_${w}_$rep.err
+    timeout 600 python bench.py --full $args --no-cpu-baseline > $OUT/bench_${w}_$rep.json 2> $OUT/bench_${w}_$rep.err
     python - <<PY
 import json
 try:

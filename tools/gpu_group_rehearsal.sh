@@ -20,7 +20,7 @@ fails=0
 run() {  # name, world, extra bench args
     local name=$1 w=$2; shift 2
     timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$w" --master-addr 127.0.0.1 \
-        --master-port $((29500 + RANDOM % 500)) bench.py --gpus "$w" --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$OUT/$name.log" 2>&1
+        --master-port $((29500 + RANDOM % 500)) bench.py --full --gpus "$w" --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$OUT/$name.log" 2>&1
     local rc=$?
     grep '^{' "$OUT/$name.log" > "$OUT/$name.json"
     python - "$OUT/$name.json" "$name" "$w" "$rc" <<'PY' || fails=$((fails + 1))
@@ -50,7 +50,7 @@ run h3_w2 2 --workload h3 --total-log2 14
 # the same without a launcher around bench.py: it starts the ranks itself / drives every slot from one process
 bare() {  # name, world, extra bench args
     local name=$1 w=$2; shift 2
-    ( unset WORLD_SIZE RANK LOCAL_RANK MASTER_PORT; timeout 900 python bench.py --gpus "$w" --steps 3 --warmup 1 "$@" > "$OUT/$name.log" 2> "$OUT/$name.err" )
+    ( unset WORLD_SIZE RANK LOCAL_RANK MASTER_PORT; timeout 900 python bench.py --full --gpus "$w" --steps 3 --warmup 1 "$@" > "$OUT/$name.log" 2> "$OUT/$name.err" )
     local rc=$?
     grep '^{' "$OUT/$name.log" > "$OUT/$name.json"
     python - "$OUT/$name.json" "$name" "$w" "$rc" <<'PY' || fails=$((fails + 1))

@@ -20,7 +20,7 @@ if has testlib; then   # the same suite once more with libposeidon_mi355x_test.s
 fi
 if has fuzz; then ( timeout 1500 python tools/diag/fuzz_configs.py 600 501; timeout 900 python tools/diag/alpha1_widths.py | grep -c "pairs: 0 of" ) > $OUT/fuzz_configs.txt 2>&1; fi
 if has smoke; then timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; fi
-B() { local name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+B() { local name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 if has bench; then
   B c2 --steps 20 --warmup 5
   B c3 --workload c3 --steps 5 --warmup 1 --cpu-seconds 6

@@ -90,7 +90,7 @@ if has pmc; then
   cp $T $R/profiles/hbm_traffic.json
 fi
 cd $R
-B() { local name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+B() { local name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 if has bench; then
   B c2 --steps 20 --warmup 5
   B c3 --workload c3 --steps 5 --warmup 1 --cpu-seconds 6
