@@ -87,7 +87,7 @@ int pmx_device_count(void);
 /* ---- pinned host memory (optional) --------------------------------------------------------------
  * The host-buffer entry points below accept any host pointer.  When a buffer is page-locked (allocated here, or
  * registered by the caller with hipHostRegister) they switch from the runtime's pageable staging to a chunked
- * H2D / kernel / D2H pipeline on two streams: 2^20 states round-trip in 3.8 ms instead of 9-15 ms. */
+ * H2D / kernel / D2H pipeline on three streams: 2^20 states round-trip in 2.5 ms instead of 9-15 ms. */
 int pmx_host_alloc(void **ptr, size_t bytes);
 int pmx_host_free(void *ptr);
 
@@ -145,7 +145,7 @@ int pmx_ctx_width(const pmx_ctx *ctx);
 #define PMX_OP_ABSORB 3
 #define PMX_OP_SQUEEZE 4
 typedef struct pmx_engine_info {
-    char engine[64];     /* e.g. "RegEngine<3,5,opt,tab>", "HybridEngine<9,5,mfma,windows of 6>", "... x passes", "QuadEngine<5>" */
+    char engine[64];     /* e.g. "QuadEngine<5>", "HybridEngine<9,5,mfma,windows of 9>", "... x passes", "LdsEngine<5>" */
     int width;           /* t */
     int threads;         /* per workgroup */
     int waves_per_simd;  /* the kernel's launch bound (what its register allocation is held to) */
@@ -153,7 +153,7 @@ typedef struct pmx_engine_info {
     int optimised;       /* 1: optimised round schedule (sparse partial rounds, normalised layers), 0: the reference's dense one */
     int row_tables;      /* 1: t-term matrix rows consume shifted tables (81 t + 18 multiplies), 0: element form (81 t + 81);
                           * window engines: how the history terms of the S-box inputs are formed - 1 shifted tables, 2 rows on the matrix cores */
-    int lane_tables;     /* 1: identity-lane updates of the sparse layers consume shifted tables */
+    int lane_tables;     /* always 0 (no engine updates sparse layers through shifted tables any more); kept for the ABI */
     int mfma_dense;      /* 1: rows of the dense layers come from the matrix cores (int8 GEMM, pmx_mfma.hpp) */
     int launches;        /* kernel launches of the call: 1, or the passes of an absorb / squeeze call on wide states (and on device-filling t = 3 calls) */
     int partial_window;  /* K > 0: the partial rounds run as windows of K S-boxes, each closed by ONE layer on the matrix cores

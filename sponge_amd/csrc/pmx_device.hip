@@ -5,7 +5,7 @@
 // 16-B-per-lane contiguous stream, whatever t is.  Round constants and the MDS matrix are wave-uniform.
 // Arithmetic: pmx_field.hpp (unsaturated 9 x 29-bit Montgomery form); round schedule: pmx_permute.hpp.
 //
-// Engines (same interface: load_states / store_states / get / set / zero / permute), one per regime:
+// Engines (same interface: unit / owns / writes_mode, load_states / store_states / get / set / zero / permute), one per regime:
 //   QuadEngine<ALPHA>          t = 3, launches of <= 32768 units (latency-bound: narrow tree levels, a handful of sponges):
 //                              one state per quad of lanes, sparse rounds three multiplications deep.
 //   HybridEngine<T, ALPHA>     t = 3..9 on the optimised schedule: state in VGPRs, the element loop of the full rounds' S-boxes rolled
@@ -13,8 +13,7 @@
 //                              (pmx_mfma.hpp: the dense layers, and the partial rounds as windows closed by one layer each).
 //   LdsEngine<ALPHA>           any width at run time (t = 2, 10..16, no partial section, a zero in the schedule's algebra): the
 //                              reference's dense schedule, state kept in LDS as [element][limb][lane], element loops rolled.
-// (Rounds 1-5 also had a register engine for t = 3 and VALU-row forms of the hybrid engine; they went in round 6, when every modulus
-// got its int8 tables.)
+// All three run the same permute / hash / compress / absorb / squeeze kernels; the hybrid engines run absorb / squeeze as passes.
 //
 // Reference semantics implemented here (file:line in /root/reference):
 //   permute        src/poseidon/mod.rs:95-118   (apply_ark :76-80, apply_s_box :63-74, apply_mds :82-93)
@@ -32,9 +31,9 @@
 #include "pmx_permute.hpp"
 #include "pmx_sponge_plan.hpp"
 
-// The file is compiled five times (Makefile, in parallel): PMX_TU = 0 holds the t = 3 register engine, the run-time-width
-// engine, the cooperative kernel and the public launchers; PMX_TU = 1 / 3 hold the hybrid engines for alpha = 5 (widths up to 6 /
-// from 7), PMX_TU = 2 / 4 the same for the generic S-box (each width x {VALU rows, matrix cores} x 7 kernels - by far the longest compile).
+// The file is compiled five times (Makefile, in parallel): PMX_TU = 0 holds the quad engine, the run-time-width engine and the
+// public launchers; PMX_TU = 1 / 3 hold the hybrid engines for alpha = 5 (widths up to 6 / from 7), PMX_TU = 2 / 4 the same for the
+// generic S-box (each width x 7 kernels - by far the longest compile).
 #ifndef PMX_TU
 #define PMX_TU 0
 #endif
@@ -42,6 +41,17 @@
 namespace pmx {
 
 extern __shared__ uint4 pmx_lds[];  // dynamic LDS, 16-byte granules
+
+// Where a unit of a call (a state, a hash row, a compression, a sponge) lives, for the engines that give every lane one unit
+// (HybridEngine, LdsEngine): unit = the global lane index; the lane holds, and so stores, every element of its state and
+// writes its sponge's mode words.  QuadEngine answers the same questions for four lanes per unit.
+template <int THREADS>
+struct LanePerUnit {
+    static constexpr int kThreads = THREADS, kUnits = THREADS;   // lanes / units per workgroup
+    __device__ __forceinline__ static size_t unit() { return (size_t)blockIdx.x * THREADS + threadIdx.x; }
+    __device__ __forceinline__ static constexpr bool owns(uint32_t /*i*/) { return true; }
+    __device__ __forceinline__ static constexpr bool writes_mode() { return true; }
+};
 
 // ------------------------------------------------------------------------------------------------
 // HybridEngine: t = 3..9 on the optimised schedule, every product by a constant on the matrix cores (pmx_mfma.hpp): the dense layers
@@ -65,10 +75,9 @@ extern __shared__ uint4 pmx_lds[];  // dynamic LDS, 16-byte granules
 // the barriers of the state store staging.  (One wave per workgroup was measured: +-0, profiles/r06/b_ab_*.)
 constexpr int kMfmaWaves = 4;
 template <int T, int ALPHA>
-struct HybridEngine {
+struct HybridEngine : LanePerUnit<64 * kMfmaWaves> {
     static_assert(T >= PMX_MFMA_MIN_T && T <= PMX_MFMA_MAX_T && mfma_window_for(T) > 0, "the window engines cover t = 3 .. 9");
     static constexpr int kWaves = kMfmaWaves;
-    static constexpr int kThreads = 64 * kWaves;
     // waves per SIMD the register allocation must allow (4: <= 128 VGPRs, 3: <= 168, 2: <= 256)
     static constexpr int kMinWaves = T <= PMX_MFMA_4WAVE_MAX_T ? 4 : T <= PMX_MFMA_3WAVE_MAX_T ? 3 : 2;
     static constexpr int kMinWavesDriver = 2;   // (the pass kernels carry the driver's walk around the permutation: held to two waves)
@@ -300,8 +309,7 @@ struct HybridEngine {
 // staging area of the coalesced ABI load/store (t x 32 B x 64 fits one buffer).
 // ------------------------------------------------------------------------------------------------
 template <int ALPHA>
-struct LdsEngine {
-    static constexpr int kThreads = 128;
+struct LdsEngine : LanePerUnit<128> {
     static constexpr int kMinWaves = 1, kMinWavesDriver = 1;
     static constexpr bool kWaveUniformOnly = false;
 
@@ -415,7 +423,116 @@ struct LdsEngine {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Kernels (identical for both engines)
+// QuadEngine: ONE state spread over a quad of lanes (pmx_permute.hpp, cooperative schedule; t = 3): lane q of a quad
+// holds state element q, lane 3 is the spare that squares in the folded sparse rounds; the values a round exchanges
+// travel by quad-broadcast DPP moves.  For latency-bound launches - the narrow levels of a tree, a handful of sponges -
+// where what is paid is the length of one permutation's dependent chain: 32 k instructions here, 58-67 k with one lane
+// per state.  LDS: the cooperative table, staged once per workgroup (256 threads = 64 states).
+// Unit g is quad threadIdx.x / 4 of its workgroup; lanes 0..2 move their element in and out, lane 0 writes the mode words.
+// Every per-unit value of a kernel (active, the mode words, the cursors of the driver) is the same in the four lanes of a
+// quad, so whole quads are active or inactive together - which permute() needs: its DPP moves read the other lanes of the quad.
+// ------------------------------------------------------------------------------------------------
+template <int ALPHA>
+struct QuadEngine {
+    static constexpr int kThreads = 256, kUnits = 64;
+    static constexpr int kMinWaves = 2, kMinWavesDriver = 2;
+    static constexpr bool kWaveUniformOnly = false;   // quads diverge as units
+
+    Rounds c;
+    FieldRt f;
+    Fe one;
+    const uint32_t *coop;
+    uint32_t q, role;
+    Fe s;   // this lane's element of its quad's state
+
+    static size_t lds_bytes(const DevConfig &d, uint32_t /*t*/) { return (size_t)d.rounds.total_rounds * 3 * kCoopElems * kFeStride * 4; }
+
+    // the table is staged by the whole workgroup behind a barrier: every kernel builds its engine before any lane can leave
+    __device__ __forceinline__ QuadEngine(const DevConfig &d, const uint32_t *consts) : c(d.rounds), f(d.field), one(d.one) {
+        f.io = consts + d.io_offset;
+        const uint32_t table_chunks = c.total_rounds * 3 * kCoopElems * kFeStride / 4;
+        const uint4 *g4 = reinterpret_cast<const uint4 *>(consts + d.coop_offset);
+        for (uint32_t k = threadIdx.x; k < table_chunks; k += kThreads) pmx_lds[k] = g4[k];
+        __syncthreads();
+        coop = reinterpret_cast<const uint32_t *>(pmx_lds);
+        q = threadIdx.x & 3;
+        role = q < 3 ? q : 2;   // lane 3 reads lane 2's entries; in the uniform rounds it shadows lane 2 (its result is never read)
+        s = fe_zero();
+    }
+
+    __device__ __forceinline__ static size_t unit() { return (size_t)blockIdx.x * kUnits + (threadIdx.x >> 2); }
+    __device__ __forceinline__ bool owns(uint32_t i) const { return q == i; }
+    __device__ __forceinline__ bool writes_mode() const { return q == 0; }   // once per sponge
+
+    // get / set / zero act on the lane's own element: the kernels ask owns(i) before they store or add into element i
+    __device__ __forceinline__ Fe get(uint32_t /*i*/) const { return s; }
+    __device__ __forceinline__ void set(uint32_t /*i*/, const Fe &v) { s = v; }
+    __device__ __forceinline__ void zero() { s = fe_zero(); }
+    __device__ __forceinline__ Fe from_abi(const Abi &x) const { return fe_from_abi_scaled(x); }      // the optimised schedule carries the ABI residue as its internal form (pmx_field.hpp: fe_from_abi_scaled)
+    __device__ __forceinline__ Abi to_abi(const Fe &x) const { return fe_to_abi_scaled(x, f); }
+
+    // lanes 0..2 of the quad of unit g read / write element q of state g (any rate / capacity split of width 3)
+    uint32_t *mine;   // (the address is formed once, by load_states, and kept for store_states)
+    __device__ __forceinline__ void load_states(uint64_t *g_states, size_t n) {
+        const size_t g = unit();
+        mine = reinterpret_cast<uint32_t *>(g_states + ((g < n ? g : 0) * 3 + role) * 4);
+        if (g < n && q < 3) s = from_abi(abi_load(mine));
+    }
+    __device__ __forceinline__ void store_states(uint64_t * /*g_states*/, size_t n) {
+        const Abi v = to_abi(s);
+        if (unit() < n && q < 3) abi_store(mine, v);
+    }
+
+    static void describe(EngineInfo &o) {
+        std::snprintf(o.engine, sizeof o.engine, "QuadEngine<%d>", ALPHA);
+        o.threads = kThreads;   // 64 states, one per quad of lanes
+        o.optimised = 1;        // element form, sparse rounds folded three multiplications deep
+        o.row_tables = o.lane_tables = o.mfma_dense = 0;
+    }
+
+    // element held by lane `lane` of this quad, in every lane
+    template <int LANE>
+    __device__ __forceinline__ static Fe quad(const Fe &v) {
+        Fe r;
+#pragma unroll
+        // quad_perm [l, l, l, l]; every lane reads a live lane of its own quad, so there is no "old" value to keep: mov_dpp,
+        // not update_dpp(0, ...), which costs a v_mov_b32 of the 0 before every move (27 per round on a lone wave's chain)
+        for (int w = 0; w < kN; ++w) r.l[w] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.l[w], LANE * 0x55, 0xf, 0xf, false);
+        return r;
+    }
+
+    // the whole state every time (the arguments are the window engines' hints); called by whole quads (see above)
+    __device__ __forceinline__ void permute(uint32_t /*want_lo*/ = 0, uint32_t /*want_hi*/ = 3, bool /*lane0_zero*/ = false) {
+        const uint32_t first_partial = c.half_full, last_partial = c.half_full + c.partial_rounds - 1;
+        for (uint32_t r = 0; r < c.total_rounds; ++r) {
+            const uint32_t *entry = coop + ((size_t)r * 3 + role) * kCoopElems * kFeStride;
+            if (kCoopFolded<ALPHA> && r >= first_partial && r < last_partial) {   // sparse round, three multiplications deep
+                const Fe x = quad<0>(fe_add_lazy(s, fe_const(entry)));
+                const Fe res_a = coop_fold_a(q, x, entry, f);
+                const Fe res_b = coop_fold_b(q, s, res_a, entry, f);
+                Fe xpow = res_b;
+#pragma unroll
+                for (int k = 0; k < kCoopExtraSquarings<ALPHA>; ++k) xpow = mont_sqr(xpow, f);
+                s = coop_fold_c(q, s, quad<3>(xpow), res_a, quad<1>(res_b), quad<2>(res_b), f);
+                continue;
+            }
+            const Fe z = coop_pre<ALPHA>(s, entry, is_full_round(r, c) || q == 0, c, one, f);
+            Fe zz[3];
+            zz[0] = quad<0>(z);
+            zz[1] = quad<1>(z);
+            zz[2] = quad<2>(z);
+            s = coop_layer_is_norm(r, c) ? coop_post_norm(zz, entry, f) : coop_post(zz, entry, f);
+        }
+        // lane 3 carries scratch values through the rounds; keep them bounded for the next call's lazy adds
+        if (q == 3) s = fe_zero();
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// Kernels (shared by the three engines).  The engine says where a unit lives: unit() and kUnits per workgroup, owns(i) - this
+// lane holds element i, so it stores it and adds an absorbed element into it - and writes_mode() - this lane writes the
+// sponge's mode words, once per sponge.  With one lane per unit (LanePerUnit) they fold to the lane index and `true`.
+// Every kernel builds its engine before any lane can leave (QuadEngine stages its table into LDS behind a barrier).
 // ------------------------------------------------------------------------------------------------
 template <class Engine>
 __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves) permute_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states, size_t n) {
@@ -448,7 +565,7 @@ __device__ __forceinline__ uint32_t absorb_elements(Engine &e, const uint64_t *r
                 const uint32_t pos = c.capacity + idx;
                 // state[capacity + idx] += element (mod.rs:128,143); normalised so the permutation's own lazy
                 // round-constant add stays within the limb bounds
-                e.set(pos, fe_normalize(fe_add_lazy(e.get(pos), x)));
+                if (e.owns(pos)) e.set(pos, fe_normalize(fe_add_lazy(e.get(pos), x)));
                 idx += 1;
                 k += 1;
             }
@@ -482,8 +599,10 @@ __device__ __forceinline__ uint32_t squeeze_elements(Engine &e, uint64_t *row, s
         if (!done) {
             const bool last = idx + rem <= c.rate;
             const uint32_t take = last ? (uint32_t)rem : c.rate - idx;
-            for (uint32_t k = 0; k < take; ++k)
-                abi_store(reinterpret_cast<uint32_t *>(row + 4 * (pos + k)), e.to_abi(e.get(c.capacity + idx + k)));
+            for (uint32_t k = 0; k < take; ++k) {
+                const uint32_t i = c.capacity + idx + k;
+                if (e.owns(i)) abi_store(reinterpret_cast<uint32_t *>(row + 4 * (pos + k)), e.to_abi(e.get(i)));
+            }
             if (last) {
                 idx += take;
                 done = true;
@@ -507,7 +626,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
                 uint64_t *__restrict__ out, size_t out_len, size_t n) {
     Engine e(d, consts);
     const Rounds &c = e.c;
-    const size_t gid = (size_t)blockIdx.x * Engine::kThreads + threadIdx.x;
+    const size_t gid = Engine::unit();
     const bool active = gid < n;
     e.zero();                                                  // CryptographicSponge::new, mod.rs:219-230
     const uint64_t *row_in = in + (active ? gid : 0) * in_len * 4;
@@ -535,7 +654,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
             Fe x = fe_zero();
             if (active) x = e.from_abi(abi_load(reinterpret_cast<const uint32_t *>(row_in + 4 * k_in)));
             const uint32_t at = c.capacity + idx;
-            e.set(at, fe_normalize(fe_add_lazy(e.get(at), x)));
+            if (e.owns(at)) e.set(at, fe_normalize(fe_add_lazy(e.get(at), x)));
             ++idx;
             ++k_in;
             continue;
@@ -550,8 +669,9 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
         const bool last = idx + rem <= c.rate;                 // squeeze_internal, mod.rs:153-182
         const uint32_t take = last ? (uint32_t)rem : c.rate - idx;
         for (uint32_t k = 0; k < take; ++k) {
-            const Abi v = e.to_abi(e.get(c.capacity + idx + k));
-            if (active) abi_store(reinterpret_cast<uint32_t *>(row_out + 4 * (pos + k)), v);
+            const uint32_t i = c.capacity + idx + k;
+            const Abi v = e.to_abi(e.get(i));
+            if (active && e.owns(i)) abi_store(reinterpret_cast<uint32_t *>(row_out + 4 * (pos + k)), v);
         }
         if (last) break;
         need = rem != c.rate;                                  // mod.rs:175, tested before the slice is advanced
@@ -571,259 +691,16 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     compress_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ in,
                     uint64_t *__restrict__ out, size_t n) {
     Engine e(d, consts);
-    const size_t gid = (size_t)blockIdx.x * Engine::kThreads + threadIdx.x;
+    const size_t gid = Engine::unit();
     const bool active = gid < n;
     const uint32_t *pair = reinterpret_cast<const uint32_t *>(in + (active ? gid : 0) * 8);
     e.zero();
-    e.set(e.c.capacity, e.from_abi(abi_load(pair)));
-    e.set(e.c.capacity + 1, e.from_abi(abi_load(pair + 8)));
+    // each input element is loaded by the lane that holds it only
+    if (e.owns(e.c.capacity)) e.set(e.c.capacity, e.from_abi(abi_load(pair)));
+    if (e.owns(e.c.capacity + 1)) e.set(e.c.capacity + 1, e.from_abi(abi_load(pair + 8)));
     e.permute(e.c.capacity, e.c.capacity + 1, e.c.capacity >= 1);   // only the digest lane of the result is read; lane 0 (capacity) went in as zero
     const Abi digest = e.to_abi(e.get(e.c.capacity));
-    if (active) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
-}
-
-// ------------------------------------------------------------------------------------------------
-// QuadEngine: ONE state spread over a quad of lanes (pmx_permute.hpp, cooperative schedule; t = 3): lane q of a quad
-// holds state element q, lane 3 is the spare that squares in the folded sparse rounds; the values a round exchanges
-// travel by quad-broadcast DPP moves.  For latency-bound launches - the narrow levels of a tree, a handful of sponges -
-// where what is paid is the length of one permutation's dependent chain: 32 k instructions here, 58-67 k with one lane
-// per state.  LDS: the cooperative table, staged once per workgroup (256 threads = 64 states).
-// ------------------------------------------------------------------------------------------------
-template <int ALPHA>
-struct QuadEngine {
-    Rounds c;
-    FieldRt f;
-    Fe one;
-    const uint32_t *coop;
-    uint32_t q, role;
-    Fe s;   // this lane's element of its quad's state
-
-    static size_t lds_bytes(const DevConfig &d) { return (size_t)d.rounds.total_rounds * 3 * kCoopElems * kFeStride * 4; }
-
-    __device__ __forceinline__ QuadEngine(const DevConfig &d, const uint32_t *consts) : c(d.rounds), f(d.field), one(d.one) {
-        f.io = consts + d.io_offset;
-        const uint32_t table_chunks = c.total_rounds * 3 * kCoopElems * kFeStride / 4;
-        const uint4 *g4 = reinterpret_cast<const uint4 *>(consts + d.coop_offset);
-        for (uint32_t k = threadIdx.x; k < table_chunks; k += 256) pmx_lds[k] = g4[k];
-        __syncthreads();
-        coop = reinterpret_cast<const uint32_t *>(pmx_lds);
-        q = threadIdx.x & 3;
-        role = q < 3 ? q : 2;   // lane 3 reads lane 2's entries; in the uniform rounds it shadows lane 2 (its result is never read)
-        s = fe_zero();
-    }
-
-    __device__ __forceinline__ Fe from_abi(const Abi &x) const { return fe_from_abi_scaled(x); }      // the optimised schedule carries the ABI residue as its internal form (pmx_field.hpp: fe_from_abi_scaled)
-    __device__ __forceinline__ Abi to_abi(const Fe &x) const { return fe_to_abi_scaled(x, f); }
-
-    // element held by lane `lane` of this quad, in every lane
-    template <int LANE>
-    __device__ __forceinline__ static Fe quad(const Fe &v) {
-        Fe r;
-#pragma unroll
-        // quad_perm [l, l, l, l]; every lane reads a live lane of its own quad, so there is no "old" value to keep: mov_dpp,
-        // not update_dpp(0, ...), which costs a v_mov_b32 of the 0 before every move (27 per round on a lone wave's chain)
-        for (int w = 0; w < kN; ++w) r.l[w] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.l[w], LANE * 0x55, 0xf, 0xf, false);
-        return r;
-    }
-
-    // callers keep whole quads active or inactive together (the DPP moves read the other lanes of the quad)
-    __device__ __forceinline__ void permute() {
-        const uint32_t first_partial = c.half_full, last_partial = c.half_full + c.partial_rounds - 1;
-        for (uint32_t r = 0; r < c.total_rounds; ++r) {
-            const uint32_t *entry = coop + ((size_t)r * 3 + role) * kCoopElems * kFeStride;
-            if (kCoopFolded<ALPHA> && r >= first_partial && r < last_partial) {   // sparse round, three multiplications deep
-                const Fe x = quad<0>(fe_add_lazy(s, fe_const(entry)));
-                const Fe res_a = coop_fold_a(q, x, entry, f);
-                const Fe res_b = coop_fold_b(q, s, res_a, entry, f);
-                Fe xpow = res_b;
-#pragma unroll
-                for (int k = 0; k < kCoopExtraSquarings<ALPHA>; ++k) xpow = mont_sqr(xpow, f);
-                s = coop_fold_c(q, s, quad<3>(xpow), res_a, quad<1>(res_b), quad<2>(res_b), f);
-                continue;
-            }
-            const Fe z = coop_pre<ALPHA>(s, entry, is_full_round(r, c) || q == 0, c, one, f);
-            Fe zz[3];
-            zz[0] = quad<0>(z);
-            zz[1] = quad<1>(z);
-            zz[2] = quad<2>(z);
-            s = coop_layer_is_norm(r, c) ? coop_post_norm(zz, entry, f) : coop_post(zz, entry, f);
-        }
-        // lane 3 carries scratch values through the rounds; keep them bounded for the next call's lazy adds
-        if (q == 3) s = fe_zero();
-    }
-};
-
-// 2-to-1 compression on the quad engine (capacity 1, rate 2): state = [0, l, r], digest = element 1.
-template <int ALPHA>
-__global__ void __launch_bounds__(256, 2)
-    compress_coop_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ in,
-                         uint64_t *__restrict__ out, size_t n) {
-    QuadEngine<ALPHA> e(d, consts);
-    const size_t g = (size_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const bool active = g < n;
-    if (active && (e.q == 1 || e.q == 2)) e.s = e.from_abi(abi_load(reinterpret_cast<const uint32_t *>(in + (g * 2 + (e.q - 1)) * 4)));
-    e.permute();
-    const Abi digest = e.to_abi(e.s);
-    if (active && e.q == 1) abi_store(reinterpret_cast<uint32_t *>(out + g * 4), digest);   // state[capacity]
-}
-
-// The permutation itself on the quad engine (any rate / capacity split of width 3: lane q holds element q).
-template <int ALPHA>
-__global__ void __launch_bounds__(256, 2)
-    permute_quad_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states, size_t n) {
-    QuadEngine<ALPHA> e(d, consts);
-    const size_t g = (size_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const bool active = g < n;
-    uint32_t *mine = reinterpret_cast<uint32_t *>(states + ((active ? g : 0) * 3 + e.role) * 4);
-    if (active && e.q < 3) e.s = e.from_abi(abi_load(mine));
-    e.permute();
-    const Abi v = e.to_abi(e.s);
-    if (active && e.q < 3) abi_store(mine, v);
-}
-
-// The fixed-shape hash on the quad engine (capacity 1, rate 2): the same wave-uniform state machine as hash_kernel.
-template <int ALPHA>
-__global__ void __launch_bounds__(256, 2)
-    hash_quad_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ in, size_t in_len,
-                     uint64_t *__restrict__ out, size_t out_len, size_t n) {
-    QuadEngine<ALPHA> e(d, consts);
-    const Rounds &c = e.c;
-    const size_t g = (size_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const bool active = g < n;
-    const uint64_t *row_in = in + (active ? g : 0) * in_len * 4;
-    uint64_t *row_out = out + (active ? g : 0) * out_len * 4;
-    size_t k_in = 0, rem = out_len, pos = 0;
-    uint32_t idx = 0;
-    bool squeezing = false, need = false;
-    for (;;) {
-        if (need) {
-            e.permute();
-            need = false;
-        }
-        if (k_in < in_len) {                                   // absorb_internal, mod.rs:121-150
-            if (idx == c.rate) {                               // rate full and more input remains
-                need = true;
-                idx = 0;
-                continue;
-            }
-            Fe x = fe_zero();
-            if (active) x = e.from_abi(abi_load(reinterpret_cast<const uint32_t *>(row_in + 4 * k_in)));
-            if (e.q == c.capacity + idx) e.s = fe_normalize(fe_add_lazy(e.s, x));
-            ++idx;
-            ++k_in;
-            continue;
-        }
-        if (!squeezing) {                                      // Absorbing -> permute, squeeze from 0 (mod.rs:324-328)
-            squeezing = true;
-            need = true;
-            idx = 0;
-            continue;
-        }
-        const bool last = idx + rem <= c.rate;                 // squeeze_internal, mod.rs:153-182
-        const uint32_t take = last ? (uint32_t)rem : c.rate - idx;
-        const Abi v = e.to_abi(e.s);
-        for (uint32_t k = 0; k < take; ++k)
-            if (active && e.q == c.capacity + idx + k) abi_store(reinterpret_cast<uint32_t *>(row_out + 4 * (pos + k)), v);
-        if (last) break;
-        need = rem != c.rate;                                  // mod.rs:175, tested before the slice is advanced
-        rem -= take;
-        pos += take;
-        idx = 0;
-    }
-}
-
-// The duplex-sponge driver on the quad engine (capacity 1, rate 2), same semantics as absorb_kernel / squeeze_kernel
-// below: a handful of sponges - the single PoseidonSponge of the trait shims - is all latency.  Mode and index are
-// per-sponge values, identical in the four lanes of a quad, so quads diverge as units.
-template <int ALPHA>
-__global__ void __launch_bounds__(256, 2)
-    absorb_quad_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states,
-                       uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, const uint64_t *__restrict__ in,
-                       size_t in_len, size_t n) {
-    QuadEngine<ALPHA> e(d, consts);
-    const size_t g = (size_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const bool active = g < n;
-    uint32_t *mine = reinterpret_cast<uint32_t *>(states + ((active ? g : 0) * 3 + e.role) * 4);
-    if (active && e.q < 3) e.s = e.from_abi(abi_load(mine));
-    uint32_t idx = 0;
-    if (active) idx = (mode_tag[g] == PMX_MODE_ABSORBING) ? mode_index[g] : e.c.rate;
-    if (idx > e.c.rate) idx = e.c.rate;                        // device-resident mode words are not validated by the host
-    const uint64_t *row = in + (active ? g : 0) * in_len * 4;
-    size_t k = active ? 0 : in_len;                            // per-sponge input cursor (see absorb_elements)
-    while (__builtin_amdgcn_ballot_w64(k < in_len)) {
-        for (uint32_t j = 0; j < e.c.rate; ++j) {
-            if (k < in_len && idx < e.c.rate) {
-                const Fe x = e.from_abi(abi_load(reinterpret_cast<const uint32_t *>(row + 4 * k)));
-                if (e.q == e.c.capacity + idx) e.s = fe_normalize(fe_add_lazy(e.s, x));   // state[capacity + idx] += element (mod.rs:128,143)
-                idx += 1;
-                k += 1;
-            }
-        }
-        const bool need = k < in_len && idx == e.c.rate;       // rate filled and more input remains (mod.rs:137-148, :241-252)
-        if (__builtin_amdgcn_ballot_w64(need)) {
-            if (need) {
-                e.permute();
-                idx = 0;
-            }
-        }
-    }
-    const Abi v = e.to_abi(e.s);
-    if (active && e.q < 3) abi_store(mine, v);
-    if (active && e.q == 0) {
-        mode_tag[g] = PMX_MODE_ABSORBING;                      // mod.rs:130-132
-        mode_index[g] = idx;
-    }
-}
-
-template <int ALPHA>
-__global__ void __launch_bounds__(256, 2)
-    squeeze_quad_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states,
-                        uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, uint64_t *__restrict__ out,
-                        size_t out_len, size_t n) {
-    QuadEngine<ALPHA> e(d, consts);
-    const size_t g = (size_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const bool active = g < n;
-    uint32_t *mine = reinterpret_cast<uint32_t *>(states + ((active ? g : 0) * 3 + e.role) * 4);
-    if (active && e.q < 3) e.s = e.from_abi(abi_load(mine));
-    uint32_t idx = 0;
-    bool need = true;                                          // Absorbing -> permute, start at 0 (mod.rs:324-328)
-    if (active && mode_tag[g] == PMX_MODE_SQUEEZING) {         // mod.rs:330-336
-        idx = mode_index[g];
-        if (idx > e.c.rate) idx = e.c.rate;
-        need = idx == e.c.rate;
-        if (need) idx = 0;
-    }
-    uint64_t *row = out + (active ? g : 0) * out_len * 4;
-    size_t rem = out_len, pos = 0;
-    bool done = !active;
-    while (__builtin_amdgcn_ballot_w64(!done)) {               // squeeze_internal, mod.rs:153-182
-        const bool do_perm = !done && need;
-        if (__builtin_amdgcn_ballot_w64(do_perm)) {
-            if (do_perm) e.permute();
-        }
-        if (!done) {
-            const bool last = idx + rem <= e.c.rate;
-            const uint32_t take = last ? (uint32_t)rem : e.c.rate - idx;
-            const Abi v = e.to_abi(e.s);                 // every lane converts its own element; the matching one stores
-            for (uint32_t k = 0; k < take; ++k)
-                if (e.q == e.c.capacity + idx + k) abi_store(reinterpret_cast<uint32_t *>(row + 4 * (pos + k)), v);
-            if (last) {
-                idx += take;
-                done = true;
-            } else {
-                need = rem != e.c.rate;                        // mod.rs:175, tested before the slice is advanced
-                rem -= take;
-                pos += take;
-                idx = 0;
-            }
-        }
-    }
-    const Abi v = e.to_abi(e.s);
-    if (active && e.q < 3) abi_store(mine, v);
-    if (active && e.q == 0) {
-        mode_tag[g] = PMX_MODE_SQUEEZING;                      // mod.rs:162-164
-        mode_index[g] = idx;
-    }
+    if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
 }
 
 template <class Engine>
@@ -833,7 +710,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWavesDriver)
                   size_t in_len, size_t n) {
     static_assert(!Engine::kWaveUniformOnly, "this engine's permutation cannot run under the per-lane EXEC masks of absorb_elements");
     Engine e(d, consts);
-    const size_t gid = (size_t)blockIdx.x * Engine::kThreads + threadIdx.x;
+    const size_t gid = Engine::unit();
     const bool active = gid < n;
     e.load_states(states, n);
     uint32_t idx = 0;
@@ -841,7 +718,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWavesDriver)
     if (idx > e.c.rate) idx = e.c.rate;                        // device-resident mode words are not validated by the host
     idx = absorb_elements(e, in + (active ? gid : 0) * in_len * 4, in_len, idx, active);
     e.store_states(states, n);
-    if (active) {
+    if (active && e.writes_mode()) {
         mode_tag[gid] = PMX_MODE_ABSORBING;                    // mod.rs:130-132
         mode_index[gid] = idx;
     }
@@ -854,7 +731,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWavesDriver)
                    size_t out_len, size_t n) {
     static_assert(!Engine::kWaveUniformOnly, "this engine's permutation cannot run under the per-lane EXEC masks of squeeze_elements");
     Engine e(d, consts);
-    const size_t gid = (size_t)blockIdx.x * Engine::kThreads + threadIdx.x;
+    const size_t gid = Engine::unit();
     const bool active = gid < n;
     e.load_states(states, n);
     uint32_t idx = 0;
@@ -867,7 +744,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWavesDriver)
     }
     idx = squeeze_elements(e, out + (active ? gid : 0) * out_len * 4, out_len, idx, need, active);
     e.store_states(states, n);
-    if (active) {
+    if (active && e.writes_mode()) {
         mode_tag[gid] = PMX_MODE_SQUEEZING;                    // mod.rs:162-164
         mode_index[gid] = idx;
     }
@@ -1035,7 +912,7 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
 // ------------------------------------------------------------------------------------------------
 template <class Engine>
 struct Launch {
-    static int grid(size_t n) { return (int)((n + Engine::kThreads - 1) / Engine::kThreads); }
+    static int grid(size_t n) { return (int)((n + Engine::kUnits - 1) / Engine::kUnits); }
     static size_t lds(const DevConfig &c, uint32_t t) { return Engine::lds_bytes(c, t); }
     // more than 64 KiB of dynamic LDS has to be asked for per kernel (and device)
     template <class K>
@@ -1217,7 +1094,7 @@ PMX_HYB_DECL(hybrid5w_)
 PMX_HYB_DECL(hybridgn_)
 PMX_HYB_DECL(hybridgw_)
 
-// Engine choice (round 6: three engines, one per regime - the register engine of t = 3 and the VALU-row hybrids of rounds 1-4 are gone):
+// Engine choice (three engines, one per regime):
 //   QuadEngine     t = 3, at most 32768 units: one state per quad of lanes - the call is one permutation's latency
 //   HybridEngine   t = 3 .. 9, configs that have the window tables (DevConfig::mfma_dense: the optimised schedule exists, at least two
 //                  full rounds, the window algebra meets no zero - every config of the reference's tables, any modulus): alpha = 5
@@ -1231,11 +1108,12 @@ static bool window_engine(const DevConfig &c, uint32_t t) {
 }
 // the window engine of a width: the exponent's half of the family, then the width's
 #define PMX_WINDOW(CALL) (c.rounds.alpha == 5 ? (t <= 6 ? hybrid5n_##CALL : hybrid5w_##CALL) : (t <= 6 ? hybridgn_##CALL : hybridgw_##CALL))
-#define PMX_LDS_ENGINE(CALL)                                                 \
+// the quad or run-time-width engine of the config's exponent
+#define PMX_BY_ALPHA(ENGINE, CALL)                                           \
     do {                                                                     \
-        if (c.rounds.alpha == 5) return Launch<LdsEngine<5>>::CALL;          \
-        if (c.rounds.alpha == 17) return Launch<LdsEngine<17>>::CALL;        \
-        return Launch<LdsEngine<0>>::CALL;                                   \
+        if (c.rounds.alpha == 5) return Launch<ENGINE<5>>::CALL;             \
+        if (c.rounds.alpha == 17) return Launch<ENGINE<17>>::CALL;           \
+        return Launch<ENGINE<0>>::CALL;                                      \
     } while (0)
 
 // the quad engine's table exists (t = 3, optimised schedule) and fits LDS; the lane of each element is fixed by the
@@ -1249,73 +1127,56 @@ static bool quad_shape(const DevConfig &c, uint32_t t) { return quad_table(c, t)
 // instead of 55 k instructions: 0.066 ms up to 4096 states, 0.078 at 2^14, 0.132 at 2^15; above, the one-lane-per-state engine fills the
 // chip better - profiles/r05/v_ab_t3_engine_threshold_32769.txt, w_ab_quad_kernels_up_to_16384_only_not_kept.txt).
 static constexpr size_t kQuadMaxUnits = 32768;
-#define PMX_QUAD_LAUNCH(KERNEL, ...)                                                                                        \
-    do {                                                                                                                    \
-        const dim3 grid_((unsigned)((n + 63) / 64));                                                                        \
-        if (c.rounds.alpha == 5) hipLaunchKernelGGL(KERNEL<5>, grid_, dim3(256), QuadEngine<5>::lds_bytes(c), st, c, c.consts, __VA_ARGS__);        \
-        else if (c.rounds.alpha == 17) hipLaunchKernelGGL(KERNEL<17>, grid_, dim3(256), QuadEngine<17>::lds_bytes(c), st, c, c.consts, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<0>, grid_, dim3(256), QuadEngine<0>::lds_bytes(c), st, c, c.consts, __VA_ARGS__);    \
-        return hipGetLastError();                                                                                           \
-    } while (0)
 
 hipError_t launch_permute(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st) {
-    if (quad_table(c, t) && n <= kQuadMaxUnits) PMX_QUAD_LAUNCH(permute_quad_kernel, states, n);
+    if (quad_table(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, permute(c, t, states, n, st));
     if (window_engine(c, t)) return PMX_WINDOW(permute(c, t, states, n, st));
-    PMX_LDS_ENGINE(permute(c, t, states, n, st));
+    PMX_BY_ALPHA(LdsEngine, permute(c, t, states, n, st));
 }
 hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len,
                        size_t n, hipStream_t st) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_QUAD_LAUNCH(hash_quad_kernel, in, in_len, out, out_len, n);
+    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, hash(c, t, in, in_len, out, out_len, n, st));
     if (window_engine(c, t)) return PMX_WINDOW(hash(c, t, in, in_len, out, out_len, n, st));
-    PMX_LDS_ENGINE(hash(c, t, in, in_len, out, out_len, n, st));
+    PMX_BY_ALPHA(LdsEngine, hash(c, t, in, in_len, out, out_len, n, st));
 }
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
     // (the split (rate 3, capacity 0) of the same width takes the one-lane-per-state engine at every level)
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_QUAD_LAUNCH(compress_coop_kernel, in, out, n);
+    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, compress(c, t, in, out, n, st));
     if (window_engine(c, t)) return PMX_WINDOW(compress(c, t, in, out, n, st));
-    PMX_LDS_ENGINE(compress(c, t, in, out, n, st));
+    PMX_BY_ALPHA(LdsEngine, compress(c, t, in, out, n, st));
 }
 hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_QUAD_LAUNCH(absorb_quad_kernel, states, tag, index, in, in_len, n);
+    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, absorb(c, t, states, tag, index, in, in_len, n, st));
     if (window_engine(c, t)) return PMX_WINDOW(absorb(c, t, states, tag, index, in, in_len, n, st, scratch));
-    PMX_LDS_ENGINE(absorb(c, t, states, tag, index, in, in_len, n, st, scratch));
+    PMX_BY_ALPHA(LdsEngine, absorb(c, t, states, tag, index, in, in_len, n, st, scratch));
 }
 hipError_t launch_squeeze(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                           uint64_t *out, size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_QUAD_LAUNCH(squeeze_quad_kernel, states, tag, index, out, out_len, n);
+    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, squeeze(c, t, states, tag, index, out, out_len, n, st));
     if (window_engine(c, t)) return PMX_WINDOW(squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
-    PMX_LDS_ENGINE(squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
+    PMX_BY_ALPHA(LdsEngine, squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
 }
 
 // ---- pmx_ctx_engine_info: the same conditions, describing instead of launching ------------------------------------------
-static hipError_t describe_quad(const DevConfig &c, EngineInfo *o) {
-    std::snprintf(o->engine, sizeof o->engine, "QuadEngine<%d>", c.rounds.alpha == 5 ? 5 : c.rounds.alpha == 17 ? 17 : 0);
-    o->threads = 256;            // 64 states, one per quad of lanes
-    o->waves_per_simd = 2;       // __launch_bounds__(256, 2)
-    o->lds_bytes = (uint32_t)QuadEngine<0>::lds_bytes(c);
-    o->optimised = 1;            // element form, sparse rounds folded three multiplications deep
-    o->launches = 1;
-    return hipSuccess;
-}
 hipError_t describe_launch(const DevConfig &c, uint32_t t, int op, size_t n, size_t len, EngineInfo *o) {
     std::memset(o, 0, sizeof *o);
     o->width = (int)t;
     switch (op) {
         case PMX_OP_PERMUTE:
-            if (quad_table(c, t) && n <= kQuadMaxUnits) return describe_quad(c, o);
+            if (quad_table(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, describe(c, t, op, len, o));
             break;
         case PMX_OP_HASH:
         case PMX_OP_ABSORB:
         case PMX_OP_SQUEEZE:
         case PMX_OP_COMPRESS:
-            if (quad_shape(c, t) && n <= kQuadMaxUnits) return describe_quad(c, o);
+            if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, describe(c, t, op, len, o));
             break;
         default:
             return hipErrorInvalidValue;
     }
     if (window_engine(c, t)) return PMX_WINDOW(describe(c, t, op, len, o));
-    PMX_LDS_ENGINE(describe(c, t, op, len, o));
+    PMX_BY_ALPHA(LdsEngine, describe(c, t, op, len, o));
 }
 
 // ---- authentication paths (pmx_merkle_verify_paths_dev) --------------------------------------------------------------

@@ -245,8 +245,8 @@ PMX_FN Fe mont_mul(const Fe &a, const Fe &b, const FieldRt &f) { return mont_dot
 // a * b * 2^-261 + s  in one pass: the addend enters the upper columns of the product (as s * 2^261 before the
 // reduction), so the sum comes out with normalised limbs and no separate addition / magnitude-cap pass.
 // a lazy, b norm, s norm with value < 2^261 - 2p.  Result norm, B < Ba * Bb * p / 2^261 + Bs + 1: the accumulator
-// this is used for (identity lanes of the sparse partial rounds) grows by about one p per round; the number of
-// rounds is bounded by the host (pmx_prepare.hpp: opt_schedule_lane_headroom).
+// this is used for (the last step of the quad engine's folded rounds, pmx_permute.hpp: coop_fold_c) grows by about
+// one p per round; the number of rounds is bounded by the host (pmx_prepare.hpp: opt_schedule_lane_headroom).
 PMX_FN Fe mont_mul_add(const Fe &a, const Fe &b, const Fe &s, const FieldRt &f) {
     uint32_t m[kN];
     Fe out;
@@ -353,8 +353,8 @@ PMX_FN void tab_col_end(int k, uint64_t &acc, uint32_t (&m)[kTabSteps], Fe &out,
     }
 }
 
-// s[l] <- s[l] + z0 * w_l for L single constants whose tables follow each other (the identity lanes of one sparse
-// round), as ONE stream: three columns per chunk, the next lane's first chunk in flight during the last of this one
+// s[l] <- s[l] + z0 * w_l for L single constants whose tables follow each other (pmx_permute.hpp: permute_hybrid's
+// t = 3 history term, L = 1), as ONE stream: three columns per chunk, the next lane's first chunk in flight during the last of this one
 template <int L>
 PMX_FN void tab_lanes_stream(const Fe &z0, const uint32_t *tab, Fe *s, const FieldRt &f) {
     constexpr int kParts = kN / kTabChunk;   // chunks per lane
