@@ -198,8 +198,12 @@ int pmx_sponge_absorb_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, 
                             const uint64_t *in, size_t in_len, size_t n);
 int pmx_sponge_squeeze_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index,
                              uint64_t *out, size_t out_len, size_t n);
+/* Device-resident mode words are not validated: absorb takes an index above the rate as the rate and any tag other than
+ * PMX_MODE_ABSORBING as PMX_MODE_SQUEEZING, and (in_len > 0) writes back PMX_MODE_ABSORBING. */
 int pmx_sponge_absorb_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
                                 const uint64_t *d_in, size_t in_len, size_t n, void *stream);
+/* Likewise squeeze takes an index above the rate as the rate and any tag other than PMX_MODE_SQUEEZING as PMX_MODE_ABSORBING,
+ * and writes back PMX_MODE_SQUEEZING. */
 int pmx_sponge_squeeze_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
                                  uint64_t *d_out, size_t out_len, size_t n, void *stream);
 

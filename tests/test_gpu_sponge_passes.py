@@ -45,23 +45,26 @@ def _engine_info(cfg, op, n, length):
     return info
 
 
+def _modes(n, r, layout, rng):
+    """mode words of n sponges (n > 512 for `blocks`): `random` - any mode per sponge; `blocks` - whole workgroups in ONE mode"""
+    if layout == "random":
+        return rng.integers(0, 2, n).astype(np.uint32), rng.integers(0, r + 1, n).astype(np.uint32)
+    tag = np.zeros(n, dtype=np.uint32)
+    idx = np.zeros(n, dtype=np.uint32)
+    tag[256:512] = 1                       # workgroup 1: Squeezing{rate} (permutes first), workgroup 0: Absorbing{0} (does not)
+    idx[256:512] = r
+    tag[512:] = rng.integers(0, 2, n - 512)
+    idx[512:] = rng.integers(0, r + 1, n - 512)
+    return tag, idx
+
+
 def _run_script(f, cfg, cr, rate, capacity, n, layout, seed):
     """absorbs and squeezes of every interesting length on n sponges in mixed modes; every sponge against the C restatement"""
     t, r = rate + capacity, rate
     rng = np.random.default_rng(seed)
     batch = S.BatchPoseidonSponge.new(cfg, n)
     batch.state = synth.random_elements(f, n * t, seed=7 + rate).reshape(n, t, 4)
-    if layout == "random":
-        batch.mode_tag = rng.integers(0, 2, n).astype(np.uint32)
-        batch.mode_index = rng.integers(0, r + 1, n).astype(np.uint32)
-    else:
-        tag = np.zeros(n, dtype=np.uint32)
-        idx = np.zeros(n, dtype=np.uint32)
-        tag[256:512] = 1                       # workgroup 1: Squeezing{rate} (permutes first), workgroup 0: Absorbing{0} (does not)
-        idx[256:512] = r
-        tag[512:] = rng.integers(0, 2, n - 512)
-        idx[512:] = rng.integers(0, r + 1, n - 512)
-        batch.mode_tag, batch.mode_index = tag, idx
+    batch.mode_tag, batch.mode_index = _modes(n, r, layout, rng)
     ref = [(batch.state[i].copy(), int(batch.mode_tag[i]), int(batch.mode_index[i])) for i in range(n)]
     ops = [("absorb", r + 1), ("squeeze", r), ("squeeze", 0), ("absorb", r), ("squeeze", 1), ("absorb", 1), ("squeeze", 2 * r + 1),
            ("squeeze", r), ("absorb", 2 * r + 2), ("absorb", 0), ("squeeze", r - 1)]

@@ -584,7 +584,11 @@ def test_sponge_pass_plan_reproduces_the_reference_driver(hc, rate, capacity):
                 assert (ref.mode, ref.index) == (O.SQUEEZING, end), ("squeeze", tag, index, length)
 
 
-@pytest.mark.parametrize("p", [O.BLS12_381_FR, O.BN254_FR])
+PALLAS = 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001
+P25519 = (1 << 255) - 19        # its largest residues exceed 32 balanced bytes (the int8 tables store them as Y - p)
+
+
+@pytest.mark.parametrize("p", [O.BLS12_381_FR, O.BN254_FR, PALLAS, P25519])
 def test_absorb_addition_on_abi_residues(hc, p):
     """state[capacity + i] += element of the pass kernel: both operands are fully reduced Montgomery residues; their sum,
     reduced exactly, is the residue of the sum (mod.rs:128,143) - no multiplication involved."""
@@ -609,3 +613,33 @@ def test_absorb_addition_on_abi_residues(hc, p):
         got = O.from_limbs([int(x) for x in out])
         assert got == (a + b - p) % 2**256, (a, b, got)            # one subtraction of p, whatever the carry
         assert got % p == (a + b) % p or a + b - p >= 2**256       # ... which is congruent to a + b whenever the difference fits 256 bits
+
+
+@pytest.mark.parametrize("p", [O.BLS12_381_FR, O.BN254_FR, PALLAS, P25519])
+def test_per_lane_absorb_chain_at_its_stated_bounds(hc, p):
+    """The per-lane kernels' `state[capacity + i] += element` (pmx_device.hip: absorb_elements, hash_kernel) and the conversion that
+    ends a call without a permutation: to_abi*(fe_normalize(fe_add_lazy(A, from_abi*(x)))), on the scaled engines (QuadEngine,
+    HybridEngine: fe_to_abi_scaled, stated for values below 3 p - a lane after a permutation is below 1.3 p, after one more element
+    2.3 p) and on the Montgomery one (LdsEngine: fe_to_abi).  A is the lane's internal value, not reduced, anywhere below 1.3 p; x is a
+    reduced ABI residue.  The scaled form holds the residue itself (result (A + x) mod p), the Montgomery form A = v * 2^261
+    (result A * 2^-5 + x mod p)."""
+    rng = random.Random(p % 1000003)
+    top = (13 * p) // 10                                    # the stated bound of a lane after a permutation
+    mod = np.array(O.to_limbs(p), dtype=np.uint64)
+    lanes = [0, 1, 2, p - 2, p - 1, p, p + 1, p + 2, (p + top) // 2, top - 2, top - 1]
+    xs = [0, 1, 2, p - 2, p - 1]
+    pairs = [(a, x) for a in lanes for x in xs]
+    for a in lanes:                                          # raw sums of p - 1, p, p + 1, 2p - 2, 2p - 1, 2p, 2p + 1 where x is reduced
+        for total in (p - 1, p, p + 1, 2 * p - 2, 2 * p - 1, 2 * p, 2 * p + 1):
+            if 0 <= total - a < p:
+                pairs.append((a, total - a))
+    pairs += [(rng.randrange(top), rng.randrange(p)) for _ in range(300)] + [(rng.randrange(p, top), p - 1) for _ in range(100)]
+    inv32 = pow(32, -1, p)
+    for a, x in pairs:
+        assert a < top < 2**256
+        aa = np.array(O.to_limbs(a), dtype=np.uint64)
+        xx = np.array(O.to_limbs(x), dtype=np.uint64)
+        for op, want in ((5, (a + x) % p), (6, (a * inv32 + x) % p)):
+            out = np.zeros(4, dtype=np.uint64)
+            assert hc.hc_field_op(mod.ctypes.data, op, aa.ctypes.data, xx.ctypes.data, out.ctypes.data) == 0
+            assert O.from_limbs([int(v) for v in out]) == want, (op, a, x)
