@@ -83,6 +83,16 @@ extern "C" {
                                        d_in: *const u64, in_len: usize, n: usize, stream: *mut c_void) -> c_int;
     pub fn pmx_sponge_squeeze_batch_dev(ctx: *mut pmx_ctx, d_states: *mut u64, d_mode_tag: *mut u32, d_mode_index: *mut u32,
                                         d_out: *mut u64, out_len: usize, n: usize, stream: *mut c_void) -> c_int;
+    // variable-length rows: row i is input[offsets[i] .. offsets[i + 1]), offsets [n + 1]
+    pub fn pmx_hash_varlen_batch(ctx: *mut pmx_ctx, input: *const u64, offsets: *const u64, out: *mut u64, out_len: usize,
+                                 n: usize) -> c_int;
+    pub fn pmx_hash_varlen_batch_dev(ctx: *mut pmx_ctx, d_in: *const u64, d_offsets: *const u64, max_len: usize, d_out: *mut u64,
+                                     out_len: usize, n: usize, stream: *mut c_void) -> c_int;
+    pub fn pmx_sponge_absorb_varlen_batch(ctx: *mut pmx_ctx, states: *mut u64, mode_tag: *mut u32, mode_index: *mut u32,
+                                          input: *const u64, offsets: *const u64, n: usize) -> c_int;
+    pub fn pmx_sponge_absorb_varlen_batch_dev(ctx: *mut pmx_ctx, d_states: *mut u64, d_mode_tag: *mut u32, d_mode_index: *mut u32,
+                                              d_in: *const u64, d_offsets: *const u64, max_len: usize, n: usize,
+                                              stream: *mut c_void) -> c_int;
     pub fn pmx_merkle_2to1_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_leaves: usize, stream: *mut c_void) -> c_int;
     pub fn pmx_merkle_2to1_forest(ctx: *mut pmx_ctx, leaves: *const u64, n_trees: usize, leaves_per_tree: usize, nodes: *mut u64,
                                   roots: *mut u64) -> c_int;

@@ -207,6 +207,32 @@ int pmx_sponge_absorb_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mo
 int pmx_sponge_squeeze_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
                                  uint64_t *d_out, size_t out_len, size_t n, void *stream);
 
+/* ---- variable-length rows ----------------------------------------------------------------------
+ * The hash and absorb drivers with a length per row (the reference's absorb takes any number of elements per sponge and call,
+ * src/poseidon/mod.rs:232-254 with absorb_internal :121-150).  Row i of `in` is the elements in[offsets[i] .. offsets[i+1])
+ * ([*][4] u64, Montgomery form, as everywhere); offsets: [n+1] u64, non-decreasing.  Rows may be empty.
+ * hash, row i: PoseidonSponge::new; absorb(row i); squeeze_native_field_elements(out_len) (mod.rs:219-230, 232-254, 321-341);
+ *   out: [n][out_len][4].  An empty row gives what pmx_hash_batch gives with in_len = 0.  The squeeze is the driver's above: out_len
+ *   is at most 65536 rates (PMX_ERR_ARG beyond).
+ * absorb, sponge i: CryptographicSponge::absorb(row i) on (states[i], mode_tag[i], mode_index[i]), any mode.  A sponge whose row is
+ *   empty is left completely untouched - state, tag and index - also when it is Squeezing or at Absorbing{rate}: the reference
+ *   returns before the mode match (mod.rs:234-236).
+ * Host entries: offsets and mode words are validated (PMX_ERR_ARG naming the first bad row, before anything is modified); only
+ *   in[offsets[0] .. offsets[n]) is uploaded; rows of any length (a row longer than 65536 rates is absorbed in pieces - the same thing
+ *   to a duplex sponge - with the states kept on the device in between).
+ * _dev entries: max_len is the caller's bound on every row's length.  It sets the number of passes and is subject to the 65536-rate
+ *   limit of the fixed _dev driver (PMX_ERR_ARG beyond, nothing launched).  Device-resident offsets are not validated (like
+ *   device-resident mode words): a decreasing pair reads as an empty row, and a row longer than max_len is absorbed up to max_len
+ *   elements.  Alignment, the n limits and the provisos of the fixed _dev driver above hold (the pass lists and - for the hash - the n
+ *   fresh states and mode words come from the context's per-stream pool: not to be captured into a hipGraph). */
+int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uint64_t *offsets, uint64_t *out, size_t out_len, size_t n);
+int pmx_hash_varlen_batch_dev(pmx_ctx *ctx, const uint64_t *d_in, const uint64_t *d_offsets, size_t max_len, uint64_t *d_out,
+                              size_t out_len, size_t n, void *stream);
+int pmx_sponge_absorb_varlen_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, const uint64_t *in,
+                                   const uint64_t *offsets, size_t n);
+int pmx_sponge_absorb_varlen_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
+                                       const uint64_t *d_in, const uint64_t *d_offsets, size_t max_len, size_t n, void *stream);
+
 /* ---- 2-to-1 Merkle compression ------------------------------------------------------------------
  * parent = (new; absorb([left, right]); squeeze_native(1))[0]  (needs rate >= 2), level by level.
  * leaves: [n_leaves][4], n_leaves a power of two.  nodes (may be NULL): [2*n_leaves-1][4] receives the

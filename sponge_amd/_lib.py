@@ -119,6 +119,11 @@ SIGNATURES = {
                                                    ctypes.c_void_p]),
     "pmx_sponge_squeeze_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, _u64p, _sz, _sz,
                                                     ctypes.c_void_p]),
+    "pmx_hash_varlen_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, _sz]),
+    "pmx_hash_varlen_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _sz, _u64p, _sz, _sz, ctypes.c_void_p]),
+    "pmx_sponge_absorb_varlen_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, _u64p, _u64p, _sz]),
+    "pmx_sponge_absorb_varlen_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, _u64p, _u64p, _sz, _sz,
+                                                          ctypes.c_void_p]),
     "pmx_merkle_2to1": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _u64p, _u64p]),
     "pmx_merkle_2to1_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_void_p]),
     "pmx_merkle_2to1_forest": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _u64p, _u64p]),

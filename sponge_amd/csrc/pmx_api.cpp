@@ -2,6 +2,7 @@
 // See include/poseidon_mi355x.h for the contract and the reference interfaces each entry replaces.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -593,7 +594,8 @@ static hipError_t ctx_pass_scratch(void *owner, hipStream_t st, size_t bytes, ui
         if (b.recorded && b.stream == st && b.bytes >= bytes) { pick = &b; break; }
     if (!pick) {
         for (pmx_ctx::PassBlock &b : ctx->pass_pool) {      // the smallest idle block that is large enough
-            if (b.poisoned || b.bytes < bytes || (pick && pick->bytes <= b.bytes)) continue;
+            // (!recorded: held by the call that is being enqueued - the ragged hash keeps its states in one while its passes take another)
+            if (b.poisoned || !b.recorded || b.bytes < bytes || (pick && pick->bytes <= b.bytes)) continue;
             if (b.recorded && hipEventQuery(b.done) != hipSuccess) {
                 (void)hipGetLastError();                    // not ready - or not queryable (recorded into a capture): not idle
                 continue;
@@ -778,6 +780,141 @@ extern "C" int pmx_sponge_absorb_batch(pmx_ctx *ctx, uint64_t *states, uint32_t 
 extern "C" int pmx_sponge_squeeze_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index,
                                         uint64_t *out, size_t out_len, size_t n) {
     return sponge_host(ctx, states, mode_tag, mode_index, nullptr, out, out_len, n, false);
+}
+
+// ---- variable-length rows ------------------------------------------------------------------------
+// Row i of a call is in[offsets[i] .. offsets[i + 1]) (pmx_sponge_plan.hpp: varlen_row_len).  The _dev entries take the caller's bound
+// max_len on every row: it sets the passes (check_pass_count) and clamps a longer row; device-resident offsets are not validated.
+static int varlen_dev_args(const pmx_ctx *ctx, const void *d_states, const uint64_t *d_in, size_t max_len, size_t n, const char *who) {
+    if (!aligned16(d_states) || !aligned16(d_in)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    if (n > (size_t)0x7fffffff * 64 || n > 0xffffffffull) return set_error(PMX_ERR_ARG, "batch too large");
+    if (max_len > kSpongeMaxLen) return set_error(PMX_ERR_ARG, "%s: max_len %zu is too large", who, max_len);
+    return check_pass_count(ctx, PMX_OP_ABSORB, n, max_len, who);
+}
+
+extern "C" int pmx_sponge_absorb_varlen_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_tag, uint32_t *d_index, const uint64_t *d_in,
+                                                  const uint64_t *d_offsets, size_t max_len, size_t n, void *stream) {
+    if (!ctx || ((!d_states || !d_tag || !d_index || !d_offsets) && n) || (!d_in && n && max_len))
+        return set_error(PMX_ERR_ARG, "pmx_sponge_absorb_varlen_batch_dev: null pointer");
+    if (n == 0 || max_len == 0) return PMX_OK;   // every row is empty: nothing changes (mod.rs:234-236)
+    if (int rc = varlen_dev_args(ctx, d_states, d_in, max_len, n, "pmx_sponge_absorb_varlen_batch_dev")) return rc;
+    PMX_ABI_BEGIN("pmx_sponge_absorb_varlen_batch_dev")
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->pass_lock);
+    PMX_HIP(launch_absorb_varlen(ctx->dev, ctx->t, d_states, d_tag, d_index, d_in, d_offsets, max_len, n, (hipStream_t)stream,
+                                 PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+extern "C" int pmx_hash_varlen_batch_dev(pmx_ctx *ctx, const uint64_t *d_in, const uint64_t *d_offsets, size_t max_len, uint64_t *d_out,
+                                         size_t out_len, size_t n, void *stream) {
+    if (!ctx || (!d_offsets && n) || (!d_in && n && max_len) || (!d_out && n && out_len))
+        return set_error(PMX_ERR_ARG, "pmx_hash_varlen_batch_dev: null pointer");
+    if (n == 0 || out_len == 0) return PMX_OK;   // nothing to write
+    if (!aligned16(d_out)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    if (int rc = varlen_dev_args(ctx, nullptr, d_in, max_len, n, "pmx_hash_varlen_batch_dev")) return rc;
+    if (int rc = check_pass_count(ctx, PMX_OP_SQUEEZE, n, out_len, "pmx_hash_varlen_batch_dev")) return rc;
+    size_t st_bytes = 0;
+    if (int rc = batch_bytes(n, ctx->t, &st_bytes)) return rc;
+    PMX_ABI_BEGIN("pmx_hash_varlen_batch_dev")
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->pass_lock);
+    PMX_HIP(launch_hash_varlen(ctx->dev, ctx->t, d_in, d_offsets, max_len, d_out, out_len, n, (hipStream_t)stream,
+                               PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// The host entries: offsets (and the mode words) are validated before anything is modified; only in[offsets[0] .. offsets[n]) is uploaded.
+// A row longer than kMaxPasses rates is absorbed in pieces of at most that many elements (absorb(a ++ b) = absorb(a); absorb(b) to a duplex
+// sponge, and the empty piece of a shorter row changes nothing); the states stay on the device between pieces.
+static int varlen_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in, const uint64_t *offsets,
+                       bool hash, uint64_t *out, size_t out_len, size_t n, const char *who) {
+    PMX_ABI_BEGIN(who)
+    if (!ctx || (!offsets && n) || (!hash && (!states || !tag || !index) && n) || (hash && !out && n && out_len))
+        return set_error(PMX_ERR_ARG, "%s: null pointer", who);
+    if (n == 0 || (hash && out_len == 0)) return PMX_OK;
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i])
+            return set_error(PMX_ERR_ARG, "%s: row %zu: offsets decrease (%llu > %llu)", who, i, (unsigned long long)offsets[i],
+                             (unsigned long long)offsets[i + 1]);
+    const size_t total = offsets[n] - offsets[0];
+    if (total && !in) return set_error(PMX_ERR_ARG, "%s: null input with %zu elements", who, total);
+    int rc = PMX_OK;
+    if (!hash && (rc = check_modes(ctx, tag, index, n))) return rc;
+    if (total == 0 && !hash) return PMX_OK;   // every row empty: nothing changes (mod.rs:234-236)
+    size_t longest = 0;
+    for (size_t i = 0; i < n; ++i) longest = std::max<size_t>(longest, offsets[i + 1] - offsets[i]);
+    const size_t piece = kMaxPasses * ctx->dev.rounds.rate, pieces = longest == 0 ? 0 : (longest + piece - 1) / piece;
+    size_t st_bytes = 0, in_bytes = 0, out_bytes = 0;
+    if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(total, 1, &in_bytes)) || (rc = batch_bytes(n, hash ? out_len : 0, &out_bytes)))
+        return rc;
+    if (hash && (rc = check_pass_count(ctx, PMX_OP_SQUEEZE, n, out_len, who))) return rc;
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    // slot 0: [states | tag | index] of the n sponges; slot 1: the input (or one piece of it); slot 2: the offsets; slot 3: the digests
+    const size_t words = (n * 4 + 15) / 16 * 16;
+    void *d_sp = nullptr, *d_in = nullptr, *d_off = nullptr, *d_out = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, st_bytes + 2 * words, &d_sp))) return rc;
+    if ((rc = ctx_scratch(ctx, 1, pieces > 1 ? std::min(in_bytes, n * piece * 32) : in_bytes, &d_in))) return rc;
+    if ((rc = ctx_scratch(ctx, 2, (n + 1) * 8, &d_off))) return rc;
+    if (hash && (rc = ctx_scratch(ctx, 3, out_bytes, &d_out))) return rc;
+    uint64_t *d_st = (uint64_t *)d_sp;
+    uint32_t *d_tag = (uint32_t *)((char *)d_sp + st_bytes), *d_idx = (uint32_t *)((char *)d_sp + st_bytes + words);
+    StreamDrain drain{ctx};
+    hipStream_t st = ctx->stream;
+    if (hash) {
+        PMX_HIP(hipMemsetAsync(d_sp, 0, st_bytes + 2 * words, st));   // n fresh sponges: zero state, Absorbing{0} (mod.rs:219-230)
+    } else {
+        PMX_HIP(hipMemcpyAsync(d_st, states, st_bytes, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_tag, tag, n * 4, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_idx, index, n * 4, hipMemcpyHostToDevice, st));
+    }
+    std::vector<uint64_t> off(n + 1), packed;
+    for (size_t k = 0; k < pieces; ++k) {
+        // piece k of row i: elements [k * piece, (k + 1) * piece) of the row, rebased so that the uploaded input starts at offset 0
+        const uint64_t *src = in + offsets[0] * 4;
+        off[0] = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t len = offsets[i + 1] - offsets[i], lo = std::min(len, k * piece), hi = std::min(len, (k + 1) * piece);
+            off[i + 1] = pieces == 1 ? offsets[i + 1] - offsets[0] : off[i] + (hi - lo);
+        }
+        if (pieces > 1) {
+            packed.resize(off[n] * 4);
+            for (size_t i = 0; i < n; ++i) {
+                const size_t len = offsets[i + 1] - offsets[i], lo = std::min(len, k * piece);
+                if (off[i + 1] > off[i]) std::memcpy(packed.data() + off[i] * 4, in + (offsets[i] + lo) * 4, (off[i + 1] - off[i]) * 32);
+            }
+            src = packed.data();
+        }
+        if (off[n]) PMX_HIP(hipMemcpyAsync(d_in, src, off[n] * 32, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+        if ((rc = pmx_sponge_absorb_varlen_batch_dev(ctx, d_st, d_tag, d_idx, (const uint64_t *)d_in, (const uint64_t *)d_off,
+                                                     std::min(longest, piece), n, st)))
+            return rc;
+        PMX_HIP(hipStreamSynchronize(st));   // (`off` and `packed` are rewritten for the next piece)
+    }
+    if (hash) {
+        if ((rc = pmx_sponge_squeeze_batch_dev(ctx, d_st, d_tag, d_idx, (uint64_t *)d_out, out_len, n, st))) return rc;
+        PMX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    } else {
+        PMX_HIP(hipMemcpyAsync(states, d_st, st_bytes, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(tag, d_tag, n * 4, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(index, d_idx, n * 4, hipMemcpyDeviceToHost, st));
+    }
+    PMX_HIP(hipStreamSynchronize(st));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+extern "C" int pmx_sponge_absorb_varlen_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, const uint64_t *in,
+                                              const uint64_t *offsets, size_t n) {
+    return varlen_host(ctx, states, mode_tag, mode_index, in, offsets, false, nullptr, 0, n, "pmx_sponge_absorb_varlen_batch");
+}
+
+extern "C" int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uint64_t *offsets, uint64_t *out, size_t out_len, size_t n) {
+    return varlen_host(ctx, nullptr, nullptr, nullptr, in, offsets, true, out, out_len, n, "pmx_hash_varlen_batch");
 }
 
 // ---- Merkle 2-to-1 -------------------------------------------------------------------------------

@@ -545,6 +545,57 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves) permute_k
     e.store_states(states, n);
 }
 
+// Where the input rows of an absorb call live (absorb_kernel, sponge_walk, sponge_first_kernel, permute_listed_kernel): a policy
+// that hands out one sponge's Row - its length, the address of its element `first`, whether any pass walks it and where its walk ends.
+//   RowsFixed    every row `len` elements, row i at io + i * len (pmx_sponge_absorb_batch*, and the squeeze side of every call)
+//   RowsRagged   row i is [offsets[i], offsets[i + 1]) clamped to max_len (pmx_sponge_absorb_varlen_batch*, pmx_sponge_plan.hpp):
+//                the two offsets are loaded once per sponge in front of a kernel's permutation (and again behind it: refetch); an empty
+//                row is walked by no pass, and a sponge's walk ends at ITS last pass, the one that moves the end of its row, not the call's
+struct RowsFixed {
+    size_t len;
+    struct Row {
+        size_t sponge, len;
+        __device__ __forceinline__ size_t length() const { return len; }
+        template <class P>
+        __device__ __forceinline__ P *at(P *io, uint32_t first) const { return io + (sponge * len + first) * 4; }
+        __device__ __forceinline__ static constexpr bool walks() { return true; }
+        __device__ __forceinline__ bool ends(uint32_t q, uint32_t call_last, const SpongePass &) const { return q >= call_last; }
+    };
+    __device__ __forceinline__ Row row(size_t sponge, bool /*active*/) const { return Row{sponge, len}; }
+    __device__ __forceinline__ Row refetch(size_t sponge, bool active) const { return row(sponge, active); }
+    size_t bound() const { return len; }
+};
+struct RowsRagged {
+    const uint64_t *in;        // the input: row i starts at in + offsets[i] (the kernels' own `io` argument is not read)
+    const uint64_t *offsets;   // [n + 1], device-resident, not validated (see varlen_row_len)
+    uint32_t max_len;          // the caller's bound on every row; sets the call's passes
+    struct Row {
+        const uint64_t *base;  // the row's first element
+        uint32_t len;
+        __device__ __forceinline__ size_t length() const { return len; }
+        template <class P>
+        __device__ __forceinline__ P *at(P * /*io*/, uint32_t first) const { return const_cast<P *>(base) + (size_t)first * 4; }
+        __device__ __forceinline__ bool walks() const { return absorb_row_walks(len); }
+        // (the call's last pass as a backstop: it is never reached first - pmx_sponge_plan.hpp, tests/test_varlen_plan.py)
+        __device__ __forceinline__ bool ends(uint32_t q, uint32_t call_last, const SpongePass &sp) const { return absorb_row_ends(sp, len) || q >= call_last; }
+    };
+    // (an inactive lane reads nothing: its Row is empty)
+    __device__ __forceinline__ Row row(size_t sponge, bool active) const {
+        if (!active) return Row{in, 0};
+        const uint64_t lo = offsets[sponge], hi = offsets[sponge + 1];
+        return Row{in + lo * 4, varlen_row_len(lo, hi, max_len)};
+    }
+    // the same Row behind the permutation of a pass kernel, loaded again: kept in registers across the permutation it spilled (t = 9: 12
+    // bytes of scratch in the listed kernel).
+    // The empty asm makes the pointer opaque, so that the compiler issues the two loads again instead of keeping the first ones.
+    __device__ __forceinline__ Row refetch(size_t sponge, bool active) const {
+        RowsRagged again = *this;
+        asm volatile("" : "+s"(again.offsets));
+        return again.row(sponge, active);
+    }
+    size_t bound() const { return max_len; }
+};
+
 // absorb `in_len` elements into this lane's sponge; idx is the next absorb index, or `rate` to force the
 // permutation a Squeezing sponge performs first (mod.rs:247-252).  Returns the final next_absorb_index.
 // The reference walks the input element by element and permutes whenever the rate is full and more input remains
@@ -703,22 +754,25 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
 }
 
-template <class Engine>
+// (per-lane engines: every lane keeps its own cursor and length - lanes of a wave may absorb rows of different lengths; a lane whose
+// row is empty absorbs nothing and leaves its mode words alone, mod.rs:234-236)
+template <class Engine, class Rows>
 __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWavesDriver)
     absorb_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states,
                   uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, const uint64_t *__restrict__ in,
-                  size_t in_len, size_t n) {
+                  Rows rows, size_t n) {
     static_assert(!Engine::kWaveUniformOnly, "this engine's permutation cannot run under the per-lane EXEC masks of absorb_elements");
     Engine e(d, consts);
     const size_t gid = Engine::unit();
     const bool active = gid < n;
     e.load_states(states, n);
+    const typename Rows::Row row = rows.row(active ? gid : 0, active);
     uint32_t idx = 0;
     if (active) idx = (mode_tag[gid] == PMX_MODE_ABSORBING) ? mode_index[gid] : e.c.rate;
     if (idx > e.c.rate) idx = e.c.rate;                        // device-resident mode words are not validated by the host
-    idx = absorb_elements(e, in + (active ? gid : 0) * in_len * 4, in_len, idx, active);
+    idx = absorb_elements(e, row.at(in, 0), row.length(), idx, active);
     e.store_states(states, n);
-    if (active && e.writes_mode()) {
+    if (active && e.writes_mode() && row.walks()) {
         mode_tag[gid] = PMX_MODE_ABSORBING;                    // mod.rs:130-132
         mode_index[gid] = idx;
     }
@@ -765,19 +819,20 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWavesDriver)
 // Both run the permutation wave-uniform on the permutation engine of the width (the matrix-core one at t = 7..9) with
 // nothing per-sponge live across it but one ballot; and from the second permutation on a batch in mixed modes costs the
 // permutations the reference would execute, not max-over-a-wave of them.
-template <bool SQUEEZE>
+template <bool SQUEEZE, class Row>
 __device__ __forceinline__ bool sponge_walk(const Rounds &c, const uint32_t *__restrict__ p32, uint64_t *__restrict__ states, uint32_t *__restrict__ mode_tag,
-                                            uint32_t *__restrict__ mode_index, uint64_t *__restrict__ io, size_t len, size_t sponge, bool active,
-                                            uint32_t pass, uint32_t last_pass, bool first_move_done = false) {
-    if (!active) return false;
+                                            uint32_t *__restrict__ mode_index, uint64_t *__restrict__ io, const Row &rw, size_t sponge, bool active,
+                                            uint32_t pass, uint32_t call_last_pass, bool first_move_done = false) {
+    if (!active || !rw.walks()) return false;   // (an empty ragged row: the sponge is not touched at all)
     const uint32_t tag = mode_tag[sponge], index = mode_index[sponge], t_all = c.rate + c.capacity;
+    const uint32_t len = (uint32_t)rw.length();
     for (uint32_t q = pass;; ++q) {
-        const SpongePass sp = SQUEEZE ? squeeze_pass(tag, index, (uint32_t)len, c.rate, c.capacity, q) : absorb_pass(tag, index, (uint32_t)len, c.rate, c.capacity, q);
+        const SpongePass sp = SQUEEZE ? squeeze_pass(tag, index, len, c.rate, c.capacity, q) : absorb_pass(tag, index, len, c.rate, c.capacity, q);
         // absorb: the chunk in front of a permutation is added by the kernel that permutes, as the state comes into its
         // registers (AbsorbAdjust) - only a chunk no permutation follows is added here, in memory
         if (!SQUEEZE && sp.permute) return true;
         uint32_t *st = reinterpret_cast<uint32_t *>(states + (sponge * t_all + sp.state_pos) * 4);
-        uint32_t *row = reinterpret_cast<uint32_t *>(io + (sponge * len + sp.first) * 4);
+        uint32_t *row = reinterpret_cast<uint32_t *>(rw.at(io, sp.first));
         // squeeze: the chunk right behind a permutation was copied out of the LDS staging by the kernel that permuted (CopyOut)
         const uint32_t todo = (SQUEEZE && first_move_done && q == pass) ? 0 : sp.count;
         for (uint32_t j = 0; j < todo; ++j) {
@@ -789,7 +844,7 @@ __device__ __forceinline__ bool sponge_walk(const Rounds &c, const uint32_t *__r
             }
         }
         if (sp.permute) return true;   // its permutation q follows: only q == pass can get here (permutations are numbered consecutively)
-        if (q >= last_pass) {          // the call is over for this sponge
+        if (rw.ends(q, call_last_pass, sp)) {   // the call is over for this sponge
             mode_tag[sponge] = SQUEEZE ? PMX_MODE_SQUEEZING : PMX_MODE_ABSORBING;
             mode_index[sponge] = sp.end_index;
             return false;
@@ -812,14 +867,15 @@ __device__ __forceinline__ void sponge_queue(bool queued, size_t sponge, uint32_
 // Pass 0 over the whole batch, in place: most calls send (nearly) every sponge through a first permutation - any absorb that
 // overflows the rate, any squeeze of an absorbing sponge - so it is not worth a list; a workgroup none of whose sponges
 // permutes leaves early, and the moves in front of the permutation hide under the other workgroups' arithmetic.
-template <class Engine, bool SQUEEZE>
+template <class Engine, bool SQUEEZE, class Rows>
 __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     sponge_first_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states,
-                        uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, uint64_t *__restrict__ io, size_t len, size_t n,
+                        uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, uint64_t *__restrict__ io, Rows rows, size_t n,
                         uint32_t last_pass, uint32_t *__restrict__ list1, uint32_t *__restrict__ count1) {
     const size_t gid = (size_t)blockIdx.x * Engine::kThreads + threadIdx.x;
     const uint32_t *p32 = consts + d.io_offset + kIoP32;   // the modulus as 8 x 32-bit limbs (wave-uniform: scalar loads)
-    const bool due = sponge_walk<SQUEEZE>(d.rounds, p32, states, mode_tag, mode_index, io, len, gid, gid < n, 0, last_pass);
+    const typename Rows::Row row = rows.row(gid, gid < n);
+    const bool due = sponge_walk<SQUEEZE>(d.rounds, p32, states, mode_tag, mode_index, io, row, gid, gid < n, 0, last_pass);
     const uint64_t due_mask = __builtin_amdgcn_ballot_w64(due);       // wave-uniform: the only thing live across the permutation
     {   // workgroup vote through the first word of the DYNAMIC LDS (free until the engine is built): __syncthreads_or keeps a static
         // word of its own, which would come on top of the engine's dynamic LDS (72 KiB at t = 9: two workgroups per CU)
@@ -836,8 +892,8 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
         Engine e(d, consts);
         typename Engine::AbsorbAdjust add{nullptr, p32, 0, 0};
         if (!SQUEEZE && due) {   // the chunk in front of this sponge's permutation 0 (none if its mode asks for the permutation up front)
-            const SpongePass sp = absorb_pass(mode_tag[gid], mode_index[gid], (uint32_t)len, d.rounds.rate, d.rounds.capacity, 0);
-            add.row = reinterpret_cast<const uint32_t *>(io + (gid * len + sp.first) * 4);
+            const SpongePass sp = absorb_pass(mode_tag[gid], mode_index[gid], (uint32_t)row.length(), d.rounds.rate, d.rounds.capacity, 0);
+            add.row = reinterpret_cast<const uint32_t *>(row.at(io, sp.first));
             add.pos = sp.state_pos;
             add.count = sp.count;
         }
@@ -845,8 +901,8 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
         e.permute(0, e.c.rate + e.c.capacity);   // (run-time width: see permute_kernel)
         typename Engine::CopyOut out{nullptr, 0, 0};
         if (SQUEEZE && ((due_mask >> (threadIdx.x & 63)) & 1)) {   // the chunk right behind permutation 0
-            const SpongePass sp = squeeze_pass(mode_tag[gid], mode_index[gid], (uint32_t)len, d.rounds.rate, d.rounds.capacity, 1);
-            out.row = reinterpret_cast<uint32_t *>(io + (gid * len + sp.first) * 4);
+            const SpongePass sp = squeeze_pass(mode_tag[gid], mode_index[gid], (uint32_t)row.length(), d.rounds.rate, d.rounds.capacity, 1);
+            out.row = reinterpret_cast<uint32_t *>(row.at(io, sp.first));
             out.pos = sp.state_pos;
             out.count = sp.count;
         }
@@ -855,14 +911,15 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     const bool mine_due = (due_mask >> (threadIdx.x & 63)) & 1;
     // (the wave's span was written by other lanes of the SAME wave after a workgroup barrier: make it visible to this lane's loads)
     __threadfence_block();
-    const bool again = sponge_walk<SQUEEZE>(d.rounds, p32, states, mode_tag, mode_index, io, len, gid, mine_due, 1, last_pass, true);
+    const typename Rows::Row row_after = rows.refetch(gid, gid < n);
+    const bool again = sponge_walk<SQUEEZE>(d.rounds, p32, states, mode_tag, mode_index, io, row_after, gid, mine_due, 1, last_pass, true);
     sponge_queue(again, gid, list1, count1);
 }
 
-template <class Engine, bool SQUEEZE>
+template <class Engine, bool SQUEEZE, class Rows>
 __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     permute_listed_kernel(const DevConfig d, const uint32_t *__restrict__ consts, uint64_t *__restrict__ states,
-                          uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, uint64_t *__restrict__ io, size_t len,
+                          uint32_t *__restrict__ mode_tag, uint32_t *__restrict__ mode_index, uint64_t *__restrict__ io, Rows rows,
                           uint32_t pass, uint32_t last_pass, const uint32_t *__restrict__ list, const uint32_t *__restrict__ list_count,
                           uint32_t *__restrict__ list_next, uint32_t *__restrict__ count_next) {
     // The count and the list were produced by the atomics and stores of the PREVIOUS launch, at addresses an earlier launch of
@@ -874,14 +931,15 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     const size_t slot = (size_t)blockIdx.x * Engine::kThreads + threadIdx.x;
     const bool active = slot < count;
     const size_t sponge = __hip_atomic_load(const_cast<uint32_t *>(list) + (active ? slot : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const typename Rows::Row row = rows.row(sponge, active);
     {
         Engine e(d, consts);
         uint64_t *mine = states + sponge * (size_t)(e.c.rate + e.c.capacity) * 4;
         const uint32_t *p32 = consts + d.io_offset + kIoP32;
         typename Engine::AbsorbAdjust add{nullptr, p32, 0, 0};
         if (!SQUEEZE && active) {    // the chunk in front of this sponge's permutation `pass`
-            const SpongePass sp = absorb_pass(mode_tag[sponge], mode_index[sponge], (uint32_t)len, d.rounds.rate, d.rounds.capacity, pass);
-            add.row = reinterpret_cast<const uint32_t *>(io + (sponge * len + sp.first) * 4);
+            const SpongePass sp = absorb_pass(mode_tag[sponge], mode_index[sponge], (uint32_t)row.length(), d.rounds.rate, d.rounds.capacity, pass);
+            add.row = reinterpret_cast<const uint32_t *>(row.at(io, sp.first));
             add.pos = sp.state_pos;
             add.count = sp.count;
         }
@@ -889,8 +947,8 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
         e.permute(0, e.c.rate + e.c.capacity);   // (run-time width: see permute_kernel)
         typename Engine::CopyOut out{nullptr, 0, 0};
         if (SQUEEZE && active) {     // the chunk right behind it
-            const SpongePass sp = squeeze_pass(mode_tag[sponge], mode_index[sponge], (uint32_t)len, d.rounds.rate, d.rounds.capacity, pass + 1);
-            out.row = reinterpret_cast<uint32_t *>(io + (sponge * len + sp.first) * 4);
+            const SpongePass sp = squeeze_pass(mode_tag[sponge], mode_index[sponge], (uint32_t)row.length(), d.rounds.rate, d.rounds.capacity, pass + 1);
+            out.row = reinterpret_cast<uint32_t *>(row.at(io, sp.first));
             out.pos = sp.state_pos;
             out.count = sp.count;
         }
@@ -903,7 +961,8 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     }
     // (written through the wave's LDS region by the lanes of the SAME wave: make it visible to this lane's loads)
     __threadfence_block();
-    const bool again = sponge_walk<SQUEEZE>(d.rounds, consts + d.io_offset + kIoP32, states, mode_tag, mode_index, io, len, sponge, active, pass + 1, last_pass, true);
+    const typename Rows::Row row_after = rows.refetch(sponge, active);
+    const bool again = sponge_walk<SQUEEZE>(d.rounds, consts + d.io_offset + kIoP32, states, mode_tag, mode_index, io, row_after, sponge, active, pass + 1, last_pass, true);
     sponge_queue(again, sponge, list_next, count_next);
 }
 
@@ -941,8 +1000,14 @@ struct Launch {
     }
     static hipError_t absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                              const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch & = PassScratch{}) {
-        hipLaunchKernelGGL(absorb_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, states, tag, index, in, in_len, n);
+        hipLaunchKernelGGL((absorb_kernel<Engine, RowsFixed>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                           c.consts, states, tag, index, in, RowsFixed{in_len}, n);
+        return hipGetLastError();
+    }
+    static hipError_t absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
+                                    const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch & = PassScratch{}) {
+        hipLaunchKernelGGL((absorb_kernel<Engine, RowsRagged>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                           c.consts, states, tag, index, in, RowsRagged{in, offsets, (uint32_t)max_len}, n);
         return hipGetLastError();
     }
     static hipError_t squeeze(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
@@ -954,14 +1019,16 @@ struct Launch {
     // the whole absorb / squeeze call as passes (pmx_sponge_plan.hpp): pass 0 over the batch, then one launch per further
     // permutation a sponge of the batch can need.  The two lists and the per-pass counters live in scratch the caller's
     // context keeps per stream (PassScratch).
-    template <bool SQUEEZE>
+    // (ragged rows, absorb only: `len` is the call's bound max_len, each sponge's walk ends at its own last pass)
+    template <bool SQUEEZE, class Rows = RowsFixed>
     static hipError_t sponge_passes(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, uint64_t *io,
-                                    size_t len, size_t n, hipStream_t st, const PassScratch &provider) {
+                                    const Rows &rows, size_t n, hipStream_t st, const PassScratch &provider) {
+        const size_t len = rows.bound();
         const size_t passes = SQUEEZE ? squeeze_passes(len, c.rounds.rate) : absorb_passes(len, c.rounds.rate);
         if (passes == 0 || n == 0) return hipSuccess;
         if (n > 0xffffffffull || len > kSpongeMaxLen) return hipErrorInvalidValue;
-        allow_lds(permute_listed_kernel<Engine, SQUEEZE>, Engine::lds_bytes(c, t));
-        allow_lds(sponge_first_kernel<Engine, SQUEEZE>, Engine::lds_bytes(c, t));
+        allow_lds(permute_listed_kernel<Engine, SQUEEZE, Rows>, Engine::lds_bytes(c, t));
+        allow_lds(sponge_first_kernel<Engine, SQUEEZE, Rows>, Engine::lds_bytes(c, t));
         const uint32_t last = (uint32_t)(passes - 1);    // (no sponge permutes in the last pass)
         uint32_t *scratch = nullptr;                     // [counters, padded to 64 words | list A: n | list B: n]
         const size_t head = (passes + 63) / 64 * 64;
@@ -978,13 +1045,13 @@ struct Launch {
             e = hipMemsetAsync(scratch, 0, head * 4, st);
         }
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((sponge_first_kernel<Engine, SQUEEZE>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c, c.consts,
-                               states, tag, index, io, len, n, last, lists[1], scratch ? scratch + 1 : nullptr);
+            hipLaunchKernelGGL((sponge_first_kernel<Engine, SQUEEZE, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c, c.consts,
+                               states, tag, index, io, rows, n, last, lists[1], scratch ? scratch + 1 : nullptr);
             e = hipGetLastError();
         }
         for (uint32_t p = 1; p < last && e == hipSuccess; ++p) {
-            hipLaunchKernelGGL((permute_listed_kernel<Engine, SQUEEZE>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                               c.consts, states, tag, index, io, len, p, last, lists[p & 1], scratch + p, lists[(p + 1) & 1], scratch + p + 1);
+            hipLaunchKernelGGL((permute_listed_kernel<Engine, SQUEEZE, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                               c.consts, states, tag, index, io, rows, p, last, lists[p & 1], scratch + p, lists[(p + 1) & 1], scratch + p + 1);
             e = hipGetLastError();
         }
         if (scratch && provider.done) provider.done(provider.owner, st, scratch);   // behind the last launch that reads the lists
@@ -1007,6 +1074,11 @@ struct Launch {
 #error "PMX_TU = 99 (make asm1) names its engine with -DPMX_ONE_T=<width> -DPMX_ONE_ALPHA=<5 | 0>"
 #endif
 template __global__ void permute_kernel<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>(const DevConfig, const uint32_t *__restrict__, uint64_t *__restrict__, size_t);
+#ifdef PMX_ONE_RAGGED   // (make asm1 ... EXTRA=-DPMX_ONE_RAGGED: the two ragged pass kernels of the same engine as well)
+hipError_t one_ragged(const DevConfig &c, uint64_t *s, uint32_t *tg, uint32_t *ix, uint64_t *io, const uint64_t *o, size_t n, const PassScratch &p) {
+    return Launch<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>::template sponge_passes<false>(c, PMX_ONE_T, s, tg, ix, io, RowsRagged{io, o, 8}, n, 0, p);
+}
+#endif
 #elif PMX_TU != 0
 // ---- window engines of this translation unit ------------------------------------------------------------------------
 // four translation units (they dominate the build time, so they compile in parallel): the exponent (1, 3: alpha = 5; 2, 4: any other) x the
@@ -1056,11 +1128,17 @@ hipError_t PMX_HYB_NAME(compress)(const DevConfig &c, uint32_t t, const uint64_t
 hipError_t PMX_HYB_NAME(absorb)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                                 const uint64_t *in, size_t len, size_t n, hipStream_t st, const PassScratch &scratch) {
     uint64_t *io = const_cast<uint64_t *>(in);   // (the absorb form of the pass kernel only reads `io`)
-    PMX_HYB_DISPATCH(template sponge_passes<false>(c, t, states, tag, index, io, len, n, st, scratch));
+    PMX_HYB_DISPATCH(template sponge_passes<false>(c, t, states, tag, index, io, RowsFixed{len}, n, st, scratch));
+}
+hipError_t PMX_HYB_NAME(absorb_varlen)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
+                                       const uint64_t *in, const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st,
+                                       const PassScratch &scratch) {
+    uint64_t *io = const_cast<uint64_t *>(in);
+    PMX_HYB_DISPATCH(template sponge_passes<false>(c, t, states, tag, index, io, RowsRagged{in, offsets, (uint32_t)max_len}, n, st, scratch));
 }
 hipError_t PMX_HYB_NAME(squeeze)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                                  uint64_t *out, size_t len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    PMX_HYB_DISPATCH(template sponge_passes<true>(c, t, states, tag, index, out, len, n, st, scratch));
+    PMX_HYB_DISPATCH(template sponge_passes<true>(c, t, states, tag, index, out, RowsFixed{len}, n, st, scratch));
 }
 // LDS one workgroup of the width's engine asks for (the launchers of TU 0 compare it with the device's limit)
 size_t PMX_HYB_NAME(lds_bytes)(const DevConfig &c, uint32_t t) { PMX_HYB_DISPATCH(lds(c, t)); }
@@ -1087,6 +1165,8 @@ hipError_t PMX_HYB_NAME(describe)(const DevConfig &c, uint32_t t, int op, size_t
     hipError_t P##compress(const DevConfig &, uint32_t, const uint64_t *, uint64_t *, size_t, hipStream_t);                      \
     hipError_t P##absorb(const DevConfig &, uint32_t, uint64_t *, uint32_t *, uint32_t *, const uint64_t *, size_t, size_t, hipStream_t, const PassScratch &); \
     hipError_t P##squeeze(const DevConfig &, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint64_t *, size_t, size_t, hipStream_t, const PassScratch &); \
+    hipError_t P##absorb_varlen(const DevConfig &, uint32_t, uint64_t *, uint32_t *, uint32_t *, const uint64_t *, const uint64_t *, size_t, size_t, \
+                                hipStream_t, const PassScratch &);                                                               \
     size_t P##lds_bytes(const DevConfig &, uint32_t);                                                                            \
     hipError_t P##describe(const DevConfig &, uint32_t, int, size_t, EngineInfo *);
 PMX_HYB_DECL(hybrid5n_)
@@ -1156,6 +1236,30 @@ hipError_t launch_squeeze(const DevConfig &c, uint32_t t, uint64_t *states, uint
     if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, squeeze(c, t, states, tag, index, out, out_len, n, st));
     if (window_engine(c, t)) return PMX_WINDOW(squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
     PMX_BY_ALPHA(LdsEngine, squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
+}
+// ragged rows: the engine choice of launch_absorb (quad, window engine as passes, run-time width)
+hipError_t launch_absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
+                                const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch &scratch) {
+    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st));
+    if (window_engine(c, t)) return PMX_WINDOW(absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch));
+    PMX_BY_ALPHA(LdsEngine, absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch));
+}
+// per row: new; absorb(row); squeeze_native(out_len) = n fresh sponges (Absorbing{0} and a zero state: all-zero words, mod.rs:219-230) in
+// a block of the pass pool, the ragged absorb on them, then the fixed squeeze writing straight into `out`.  (The pass form of the absorb
+// costs the permutations the reference executes; a ragged register-resident hash kernel would pay max-over-a-wave of them.)
+hipError_t launch_hash_varlen(const DevConfig &c, uint32_t t, const uint64_t *in, const uint64_t *offsets, size_t max_len, uint64_t *out,
+                              size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch) {
+    const size_t st_bytes = n * t * 32, words = (n + 3) / 4 * 4;   // (the mode words start 16-byte aligned)
+    uint32_t *block = nullptr;
+    hipError_t e = scratch.get(scratch.owner, st, st_bytes + 2 * words * 4, &block);
+    if (e != hipSuccess) return e;
+    uint64_t *states = reinterpret_cast<uint64_t *>(block);
+    uint32_t *tag = block + st_bytes / 4, *index = tag + words;
+    e = hipMemsetAsync(block, 0, st_bytes + 2 * words * 4, st);
+    if (e == hipSuccess) e = launch_absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch);
+    if (e == hipSuccess) e = launch_squeeze(c, t, states, tag, index, out, out_len, n, st, scratch);
+    scratch.done(scratch.owner, st, block);   // behind the squeeze, the last launch that reads the block
+    return e;
 }
 
 // ---- pmx_ctx_engine_info: the same conditions, describing instead of launching ------------------------------------------

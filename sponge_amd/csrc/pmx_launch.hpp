@@ -29,6 +29,13 @@ hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint3
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch);
 hipError_t launch_squeeze(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                           uint64_t *out, size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch);
+// Variable-length rows (pmx_sponge_plan.hpp: varlen_row_len): row i is in[offsets[i] .. offsets[i + 1]) clamped to max_len elements,
+// offsets [n + 1] device-resident.  absorb: an empty row leaves its sponge untouched (mod.rs:234-236).  hash: per row new; absorb(row);
+// squeeze_native(out_len) into out [n][out_len][4]; the n fresh states are a block of `scratch` (get / done once, around the call).
+hipError_t launch_absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
+                                const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch &scratch);
+hipError_t launch_hash_varlen(const DevConfig &c, uint32_t t, const uint64_t *in, const uint64_t *offsets, size_t max_len, uint64_t *out,
+                              size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch);
 
 // Authentication paths, one level per step (pmx_merkle_verify_paths_dev): pairs[i] = (cur[i], sibling) or (sibling, cur[i])
 // by bit `level` of indices[i], sibling = paths[i][level]; then ok[i] = (cur[i] == root) && indices[i] < 2^depth.

@@ -44,6 +44,22 @@ constexpr size_t kSpongeMaxLen = 0x7fffffffu;
 PMX_FN size_t absorb_passes(size_t len, uint32_t rate) { return len == 0 ? 0 : 1 + (len + rate - 1) / rate; }
 PMX_FN size_t squeeze_passes(size_t len, uint32_t rate) { return len == 0 ? 2 : 1 + (len + rate - 1) / rate; }
 
+// Variable-length rows (pmx_*_varlen_batch*): row i of a call is the input elements [offsets[i], offsets[i + 1]), each sponge with
+// a length of its own.  The device does not validate its offsets: a decreasing pair reads as an empty row, and a row is absorbed up to
+// the call's bound `max_len` (which sets the number of passes).
+PMX_FN uint32_t varlen_row_len(uint64_t lo, uint64_t hi, uint32_t max_len) {
+    return hi <= lo ? 0 : (hi - lo < (uint64_t)max_len ? (uint32_t)(hi - lo) : max_len);
+}
+// An empty row leaves its sponge untouched - state, tag and index: the reference returns before the mode match (mod.rs:234-236),
+// also for a Squeezing sponge or one at Absorbing{rate}, which a non-empty absorb would permute.  (absorb_pass has no len = 0 form:
+// its end_index would underflow.)  No pass of the call walks such a sponge.
+PMX_FN bool absorb_row_walks(uint32_t len) { return len != 0; }
+// The walk of ONE sponge's absorb(len > 0) ends, and rewrites its mode words, at its own last pass, not the call's: a 1-element row in a
+// call whose longest row is 65536 rates stops after one step instead of running through 65 k empty ones.  That pass is the one whose
+// chunk ends the row (absorb_row_ends: no division by the rate on the device), at the latest absorb_last_pass(len) - the pass at which
+// the fixed-length walk, which runs every sponge of a call to the same pass, rewrites them.
+PMX_FN uint32_t absorb_last_pass(uint32_t len, uint32_t rate) { return (uint32_t)(absorb_passes(len, rate) - 1); }
+
 // absorb(len > 0) of a sponge in mode (tag, index): mod.rs:232-254, 121-150
 PMX_FN SpongePass absorb_pass(uint32_t tag, uint32_t index, uint32_t len, uint32_t rate, uint32_t capacity, uint32_t pass) {
     if (index > rate) index = rate;                       // device-resident mode words are not validated by the host
@@ -75,6 +91,9 @@ PMX_FN SpongePass absorb_pass(uint32_t tag, uint32_t index, uint32_t len, uint32
     r.end_index = (i0 + len - 1) % rate + 1;
     return r;
 }
+
+// the move of pass `sp` (absorb_pass of a sponge's absorb(len > 0)) reaches the end of the row: nothing is left to absorb
+PMX_FN bool absorb_row_ends(const SpongePass &sp, uint32_t len) { return !sp.permute && sp.first + sp.count >= len; }
 
 // squeeze_native_field_elements(len) of a sponge in mode (tag, index): mod.rs:321-341, 153-182
 PMX_FN SpongePass squeeze_pass(uint32_t tag, uint32_t index, uint32_t len, uint32_t rate, uint32_t capacity, uint32_t pass) {

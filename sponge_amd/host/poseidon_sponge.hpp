@@ -125,6 +125,21 @@ public:
     Context &operator=(const Context &) = delete;
     pmx_ctx *get() const { return h_; }
 
+    // per row: new; absorb(rows[i]); squeeze_native_field_elements(out_len) - rows of any lengths, empty ones included
+    // (pmx_hash_varlen_batch; src/poseidon/mod.rs:219-254, 321-341).  Returns [n][out_len].
+    std::vector<Fp> hash_varlen(const std::vector<std::vector<Fp>> &rows, size_t out_len) const {
+        std::vector<Fp> in;
+        std::vector<uint64_t> offsets{0};
+        for (const auto &r : rows) {
+            in.insert(in.end(), r.begin(), r.end());
+            offsets.push_back(in.size());
+        }
+        std::vector<Fp> out(rows.size() * out_len);
+        if (rows.empty() || out_len == 0) return out;
+        check(pmx_hash_varlen_batch(h_, in.empty() ? nullptr : in[0].l.data(), offsets.data(), out[0].l.data(), out_len, rows.size()));
+        return out;
+    }
+
 private:
     pmx_ctx *h_ = nullptr;
 };
@@ -253,6 +268,19 @@ public:
         const size_t L = input.size() / n_;
         check(pmx_sponge_absorb_batch(parameters.context(device_)->get(), state[0].l.data(), mode_tag.data(), mode_index.data(),
                                       input[0].l.data(), L, n_));
+    }
+    // sponge i absorbs input[i], a row of its own length; an empty row leaves its sponge untouched (mod.rs:234-236)
+    void absorb(const std::vector<std::vector<Fp>> &input) {
+        if (input.size() != n_) throw Error(PMX_ERR_ARG, "absorb: one row per sponge");
+        std::vector<Fp> in;
+        std::vector<uint64_t> offsets{0};
+        for (const auto &r : input) {
+            in.insert(in.end(), r.begin(), r.end());
+            offsets.push_back(in.size());
+        }
+        if (n_ == 0 || in.empty()) return;
+        check(pmx_sponge_absorb_varlen_batch(parameters.context(device_)->get(), state[0].l.data(), mode_tag.data(), mode_index.data(),
+                                             in[0].l.data(), offsets.data(), n_));
     }
     std::vector<Fp> squeeze_native_field_elements(size_t num_elements) {   // [n][num_elements]
         std::vector<Fp> out(n_ * num_elements);

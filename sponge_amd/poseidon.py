@@ -169,6 +169,16 @@ def c_config(cfg: "PoseidonConfig") -> "_lib.PmxConfig":
     return c
 
 
+def varlen_rows(elems, offsets=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(elems [*][4], offsets [n+1]) of variable-length rows, contiguous u64: a list of [L_i][4] arrays (offsets None) is packed."""
+    if offsets is None:
+        rows = [np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4) for r in elems]
+        offsets = np.zeros(len(rows) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([r.shape[0] for r in rows])
+        elems = np.concatenate(rows) if rows else np.zeros((0, 4), dtype=np.uint64)
+    return np.ascontiguousarray(elems, dtype=np.uint64).reshape(-1, 4), np.ascontiguousarray(offsets, dtype=np.uint64)
+
+
 class Context:
     """pmx_ctx: one validated config resident on one GPU, taken from the library's process-wide cache
     (pmx_ctx_acquire): equal configs share one device context however many PoseidonConfig objects carry them."""
@@ -234,6 +244,22 @@ class Context:
                                                        out_len, n))
         return out
 
+    def hash_varlen_batch(self, elems, offsets=None, out_len: int = 1) -> np.ndarray:
+        """Per row i: new; absorb(elems[offsets[i] .. offsets[i+1]]); squeeze_native(out_len) (pmx_hash_varlen_batch).  `elems` is
+        [*][4] with `offsets` [n+1], or a list of [L_i][4] arrays (offsets None).  Returns [n][out_len][4]."""
+        elems, offsets = varlen_rows(elems, offsets)
+        n = offsets.shape[0] - 1
+        out = np.zeros((n, out_len, 4), dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_hash_varlen_batch(self._h, _ptr(elems) if elems.size else None, _ptr(offsets), _ptr(out), out_len, n))
+        return out
+
+    def sponge_absorb_varlen_batch(self, states, tag, index, elems, offsets=None) -> None:
+        """Sponge i absorbs elems[offsets[i] .. offsets[i+1]] (pmx_sponge_absorb_varlen_batch): states / tag / index in place; a sponge
+        whose row is empty is left untouched.  `elems`, `offsets` as in hash_varlen_batch."""
+        elems, offsets = varlen_rows(elems, offsets)
+        _lib.check(_lib.lib().pmx_sponge_absorb_varlen_batch(self._h, _ptr(states), _ptr(tag), _ptr(index),
+                                                             _ptr(elems) if elems.size else None, _ptr(offsets), offsets.shape[0] - 1))
+
     def merkle_2to1(self, leaves: np.ndarray, want_nodes: bool = True):
         leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
         m = leaves.shape[0]
@@ -269,6 +295,13 @@ class Context:
     def sponge_squeeze_batch_dev(self, d_states, d_tag, d_index, d_out, out_len, n, stream=0) -> None:
         _lib.check(_lib.lib().pmx_sponge_squeeze_batch_dev(self._h, d_states, d_tag, d_index, d_out, out_len, n, stream))
 
+    def hash_varlen_batch_dev(self, d_in, d_offsets, max_len: int, d_out, out_len: int, n: int, stream=0) -> None:
+        """d_offsets: [n+1] u64 on the device, not validated; max_len bounds every row (a longer one is absorbed up to max_len)."""
+        _lib.check(_lib.lib().pmx_hash_varlen_batch_dev(self._h, d_in, d_offsets, max_len, d_out, out_len, n, stream))
+
+    def sponge_absorb_varlen_batch_dev(self, d_states, d_tag, d_index, d_in, d_offsets, max_len: int, n: int, stream=0) -> None:
+        _lib.check(_lib.lib().pmx_sponge_absorb_varlen_batch_dev(self._h, d_states, d_tag, d_index, d_in, d_offsets, max_len, n, stream))
+
     def merkle_2to1_dev(self, d_nodes: int, n_leaves: int, stream: int = 0) -> None:
         _lib.check(_lib.lib().pmx_merkle_2to1_dev(self._h, d_nodes, n_leaves, stream))
 
@@ -303,6 +336,14 @@ class BatchPoseidonSponge:
         if L == 0:
             return                                                         # mod.rs:234-236
         self.parameters.context(self.device).sponge_absorb_batch(self.state, self.mode_tag, self.mode_index, elems, L)
+
+    def absorb_varlen(self, elems, offsets=None) -> None:
+        """Sponge i absorbs its own row elems[offsets[i] .. offsets[i+1]] (offsets [n+1]), or elems[i] of a list of n [L_i][4]
+        arrays: lengths differ per sponge, an empty row leaves its sponge untouched (mod.rs:232-254)."""
+        elems, offsets = varlen_rows(elems, offsets)
+        if offsets.shape[0] != self.n + 1:
+            raise ValueError(f"{offsets.shape[0] - 1} rows for {self.n} sponges")
+        self.parameters.context(self.device).sponge_absorb_varlen_batch(self.state, self.mode_tag, self.mode_index, elems, offsets)
 
     def squeeze_native_field_elements(self, num_elements: int) -> np.ndarray:
         """[n][num_elements][4]  (mod.rs:321-341)."""
