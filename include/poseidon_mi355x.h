@@ -27,6 +27,13 @@
  * staging buffers and streams); the *_dev entry points only enqueue on the caller's stream and may be called
  * concurrently (the absorb / squeeze ones take a short lock inside the context while they enqueue).  Distinct contexts are independent.  Every call runs with its context's device current and restores
  * the calling thread's current HIP device before it returns; a `stream` argument must belong to the context's device.
+ *
+ * Alignment of device pointers (*_dev entry points): every array of field elements - states, messages, digests, nodes, leaves,
+ * paths, the root, d_work - must be 16-byte aligned (PMX_ERR_ARG "device pointers must be 16-byte aligned" otherwise, nothing
+ * launched).  Every other array needs the natural alignment of its element type and no more: mode words (d_mode_tag, d_mode_index:
+ * uint32_t) 4 bytes, d_offsets and d_indices (uint64_t) 8 bytes, d_ok (uint8_t) any address.  Nothing beyond these is assumed: buffers
+ * carved out of one allocation at base + 16 k are as good as allocations of their own, and a call writes nothing outside the arrays
+ * it is documented to write (tests/test_gpu_footprint.py).  The host-buffer entry points accept any host pointer.
  */
 #ifndef POSEIDON_MI355X_H
 #define POSEIDON_MI355X_H
@@ -198,7 +205,7 @@ int pmx_sponge_absorb_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, 
                             const uint64_t *in, size_t in_len, size_t n);
 int pmx_sponge_squeeze_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index,
                              uint64_t *out, size_t out_len, size_t n);
-/* Device-resident mode words are not validated: absorb takes an index above the rate as the rate and any tag other than
+/* Device-resident mode words need their natural alignment (4 bytes) and are not validated: absorb takes an index above the rate as the rate and any tag other than
  * PMX_MODE_ABSORBING as PMX_MODE_SQUEEZING, and (in_len > 0) writes back PMX_MODE_ABSORBING. */
 int pmx_sponge_absorb_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
                                 const uint64_t *d_in, size_t in_len, size_t n, void *stream);
@@ -223,7 +230,7 @@ int pmx_sponge_squeeze_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_m
  * _dev entries: max_len is the caller's bound on every row's length.  It sets the number of passes and is subject to the 65536-rate
  *   limit of the fixed _dev driver (PMX_ERR_ARG beyond, nothing launched).  Device-resident offsets are not validated (like
  *   device-resident mode words): a decreasing pair reads as an empty row, and a row longer than max_len is absorbed up to max_len
- *   elements.  Alignment, the n limits and the provisos of the fixed _dev driver above hold (the pass lists and - for the hash - the n
+ *   elements.  d_offsets needs the natural alignment of uint64_t (8 bytes).  Alignment, the n limits and the provisos of the fixed _dev driver above hold (the pass lists and - for the hash - the n
  *   fresh states and mode words come from the context's per-stream pool: not to be captured into a hipGraph). */
 int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uint64_t *offsets, uint64_t *out, size_t out_len, size_t n);
 int pmx_hash_varlen_batch_dev(pmx_ctx *ctx, const uint64_t *d_in, const uint64_t *d_offsets, size_t max_len, uint64_t *d_out,
@@ -261,7 +268,8 @@ int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, 
  * pmx_merkle_verify_paths: k paths at once - one upload, `depth` level steps on the device (each a batched 2-to-1
  * compression of all k running nodes), one download: ok_out[i] = 1 iff hashing leaves[i] up its path (indices[i] says
  * left / right at each level) gives `root` and indices[i] < 2^depth.
- * pmx_merkle_verify_paths_dev: the same on device-resident buffers, enqueue only; d_work is [k][12] u64 of scratch. */
+ * pmx_merkle_verify_paths_dev: the same on device-resident buffers, enqueue only; d_work is [k][12] u64 of scratch.  d_leaves, d_paths,
+ * d_root and d_work are 16-byte aligned like every array of elements; d_indices needs 8 bytes, d_ok (k single bytes) any address. */
 int pmx_merkle_paths(const uint64_t *nodes, size_t n_leaves, const uint64_t *indices, size_t k, uint64_t *paths_out);
 int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
                             size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out);
