@@ -372,6 +372,12 @@ extern "C" int pmx_ctx_engine_info(const pmx_ctx *ctx, int op, size_t n, size_t 
 }
 
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// the argument lines the batch *_dev entries share, in the order each of them tests them (a null pointer counts as aligned)
+static int dev_batch_args(const void *a, const void *b, size_t n) {
+    if (!aligned16(a) || !aligned16(b)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    if (n > (size_t)0x7fffffff * 64) return set_error(PMX_ERR_ARG, "batch too large");
+    return PMX_OK;
+}
 
 // ---- pinned host memory ----------------------------------------------------------------------------
 extern "C" int pmx_host_alloc(void **ptr, size_t bytes) {
@@ -483,8 +489,7 @@ static size_t pipeline_rows(size_t n) {
 extern "C" int pmx_permute_batch_dev(pmx_ctx *ctx, uint64_t *d_states, size_t n, void *stream) {
     if (!ctx || (!d_states && n)) return set_error(PMX_ERR_ARG, "pmx_permute_batch_dev: null pointer");
     if (n == 0) return PMX_OK;
-    if (!aligned16(d_states)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if (n > (size_t)0x7fffffff * 64) return set_error(PMX_ERR_ARG, "batch too large");
+    if (int rc = dev_batch_args(d_states, nullptr, n)) return rc;
     PMX_BIND(ctx);
     PMX_HIP(launch_permute(ctx->dev, ctx->t, d_states, n, (hipStream_t)stream));
     return PMX_OK;
@@ -524,8 +529,7 @@ extern "C" int pmx_hash_batch_dev(pmx_ctx *ctx, const uint64_t *d_in, size_t in_
                                   size_t n, void *stream) {
     if (!ctx || (!d_in && n && in_len) || (!d_out && n && out_len)) return set_error(PMX_ERR_ARG, "pmx_hash_batch_dev: null pointer");
     if (n == 0) return PMX_OK;
-    if (!aligned16(d_in) || !aligned16(d_out)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if (n > (size_t)0x7fffffff * 64) return set_error(PMX_ERR_ARG, "batch too large");
+    if (int rc = dev_batch_args(d_in, d_out, n)) return rc;
     PMX_BIND(ctx);
     // two elements in, one out, rate >= 2: this IS the 2-to-1 compression (same memory layout as one tree level), whose
     // launcher has the quad kernel for small batches - a batch of authentication paths advances one level per call
@@ -638,19 +642,19 @@ static void ctx_pass_done(void *owner, hipStream_t st, uint32_t *block) {
         return;
     }
 }
+static PassScratch ctx_passes(pmx_ctx *ctx) { return PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}; }
 
 extern "C" int pmx_sponge_absorb_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_tag, uint32_t *d_index,
                                            const uint64_t *d_in, size_t in_len, size_t n, void *stream) {
     if (!ctx || ((!d_states || !d_tag || !d_index) && n) || (!d_in && n && in_len))
         return set_error(PMX_ERR_ARG, "pmx_sponge_absorb_batch_dev: null pointer");
     if (n == 0 || in_len == 0) return PMX_OK;  // absorbing an empty input changes nothing (mod.rs:234-236)
-    if (!aligned16(d_states) || !aligned16(d_in)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if (n > (size_t)0x7fffffff * 64) return set_error(PMX_ERR_ARG, "batch too large");
+    if (int rc = dev_batch_args(d_states, d_in, n)) return rc;
     if (int rc = check_pass_count(ctx, PMX_OP_ABSORB, n, in_len, "pmx_sponge_absorb_batch_dev")) return rc;
     PMX_ABI_BEGIN("pmx_sponge_absorb_batch_dev")
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->pass_lock);
-    PMX_HIP(launch_absorb(ctx->dev, ctx->t, d_states, d_tag, d_index, d_in, in_len, n, (hipStream_t)stream, PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}));
+    PMX_HIP(launch_absorb(ctx->dev, ctx->t, d_states, d_tag, d_index, d_in, in_len, n, (hipStream_t)stream, ctx_passes(ctx)));
     return PMX_OK;
     PMX_ABI_END
 }
@@ -660,13 +664,12 @@ extern "C" int pmx_sponge_squeeze_batch_dev(pmx_ctx *ctx, uint64_t *d_states, ui
     if (!ctx || ((!d_states || !d_tag || !d_index) && n) || (!d_out && n && out_len))
         return set_error(PMX_ERR_ARG, "pmx_sponge_squeeze_batch_dev: null pointer");
     if (n == 0) return PMX_OK;
-    if (!aligned16(d_states) || !aligned16(d_out)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if (n > (size_t)0x7fffffff * 64) return set_error(PMX_ERR_ARG, "batch too large");
+    if (int rc = dev_batch_args(d_states, d_out, n)) return rc;
     if (int rc = check_pass_count(ctx, PMX_OP_SQUEEZE, n, out_len, "pmx_sponge_squeeze_batch_dev")) return rc;
     PMX_ABI_BEGIN("pmx_sponge_squeeze_batch_dev")
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->pass_lock);
-    PMX_HIP(launch_squeeze(ctx->dev, ctx->t, d_states, d_tag, d_index, d_out, out_len, n, (hipStream_t)stream, PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}));
+    PMX_HIP(launch_squeeze(ctx->dev, ctx->t, d_states, d_tag, d_index, d_out, out_len, n, (hipStream_t)stream, ctx_passes(ctx)));
     return PMX_OK;
     PMX_ABI_END
 }
@@ -786,8 +789,8 @@ extern "C" int pmx_sponge_squeeze_batch(pmx_ctx *ctx, uint64_t *states, uint32_t
 // Row i of a call is in[offsets[i] .. offsets[i + 1]) (pmx_sponge_plan.hpp: varlen_row_len).  The _dev entries take the caller's bound
 // max_len on every row: it sets the passes (check_pass_count) and clamps a longer row; device-resident offsets are not validated.
 static int varlen_dev_args(const pmx_ctx *ctx, const void *d_states, const uint64_t *d_in, size_t max_len, size_t n, const char *who) {
-    if (!aligned16(d_states) || !aligned16(d_in)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if (n > (size_t)0x7fffffff * 64 || n > 0xffffffffull) return set_error(PMX_ERR_ARG, "batch too large");
+    if (int rc = dev_batch_args(d_states, d_in, n)) return rc;
+    if (n > 0xffffffffull) return set_error(PMX_ERR_ARG, "batch too large");
     if (max_len > kSpongeMaxLen) return set_error(PMX_ERR_ARG, "%s: max_len %zu is too large", who, max_len);
     return check_pass_count(ctx, PMX_OP_ABSORB, n, max_len, who);
 }
@@ -801,8 +804,7 @@ extern "C" int pmx_sponge_absorb_varlen_batch_dev(pmx_ctx *ctx, uint64_t *d_stat
     PMX_ABI_BEGIN("pmx_sponge_absorb_varlen_batch_dev")
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->pass_lock);
-    PMX_HIP(launch_absorb_varlen(ctx->dev, ctx->t, d_states, d_tag, d_index, d_in, d_offsets, max_len, n, (hipStream_t)stream,
-                                 PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}));
+    PMX_HIP(launch_absorb_varlen(ctx->dev, ctx->t, d_states, d_tag, d_index, d_in, d_offsets, max_len, n, (hipStream_t)stream, ctx_passes(ctx)));
     return PMX_OK;
     PMX_ABI_END
 }
@@ -820,8 +822,7 @@ extern "C" int pmx_hash_varlen_batch_dev(pmx_ctx *ctx, const uint64_t *d_in, con
     PMX_ABI_BEGIN("pmx_hash_varlen_batch_dev")
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->pass_lock);
-    PMX_HIP(launch_hash_varlen(ctx->dev, ctx->t, d_in, d_offsets, max_len, d_out, out_len, n, (hipStream_t)stream,
-                               PassScratch{ctx, ctx_pass_scratch, ctx_pass_done}));
+    PMX_HIP(launch_hash_varlen(ctx->dev, ctx->t, d_in, d_offsets, max_len, d_out, out_len, n, (hipStream_t)stream, ctx_passes(ctx)));
     return PMX_OK;
     PMX_ABI_END
 }
@@ -921,19 +922,48 @@ extern "C" int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uin
 // Level by level on the caller's stream: level l reads the n_leaves >> (l-1) nodes of level l-1 and writes
 // n_leaves >> l parents.  (Cutting the tree into subtrees on concurrent streams was measured SLOWER - 7.0 ms ->
 // 12.5 ms at 8 streams for 2^21 leaves - because the narrow levels are latency-bound, not launch-bound.)
-extern "C" int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream) {
-    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_dev: null pointer");
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
+// A single tree is the forest below with n_trees = 1: this is the level loop of both, behind each entry's own shape checks.
+static int merkle_levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t total_leaves, void *stream) {
     if (ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
     if (!aligned16(d_nodes)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
     PMX_BIND(ctx);
-    size_t src = 0, width = n_leaves;
-    while (width > 1) {
+    size_t src = 0, width = total_leaves;
+    while (width > n_trees) {      // level l of all trees: [src, src + width) -> [src + width, src + width + width / 2)
         PMX_HIP(launch_compress(ctx->dev, ctx->t, d_nodes + src * 4, d_nodes + (src + width) * 4, width / 2, (hipStream_t)stream));
         src += width;
         width /= 2;
     }
     return PMX_OK;
+}
+// Host buffers (the caller has bound the device): upload the leaves, the levels, download all nodes and / or the last n_trees (the roots).
+static int merkle_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t total_leaves, size_t n_nodes, uint64_t *nodes, uint64_t *roots) {
+    int rc = PMX_OK;
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    void *d = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d, leaves, total_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = merkle_levels_dev(ctx, (uint64_t *)d, n_trees, total_leaves, ctx->stream))) return rc;
+    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (roots) PMX_HIP(hipMemcpyAsync(roots, (uint64_t *)d + (n_nodes - n_trees) * 4, n_trees * 32, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_dev: null pointer");
+    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
+    return merkle_levels_dev(ctx, d_nodes, 1, n_leaves, stream);
+}
+
+extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_2to1")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1: null pointer");
+    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
+    PMX_BIND(ctx);
+    if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
+    return merkle_host(ctx, leaves, 1, n_leaves, 2 * n_leaves - 1, nodes, root);
+    PMX_ABI_END
 }
 
 // ---- many trees at once ------------------------------------------------------------------------------
@@ -955,16 +985,7 @@ extern "C" int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_
     if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest_dev: null pointer");
     size_t total = 0, n_nodes = 0;
     if (int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes)) return rc;
-    if (ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
-    if (!aligned16(d_nodes)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    size_t src = 0, width = total;
-    while (width > n_trees) {      // level l of all trees: [src, src + width) -> [src + width, src + width + width / 2)
-        PMX_HIP(launch_compress(ctx->dev, ctx->t, d_nodes + src * 4, d_nodes + (src + width) * 4, width / 2, (hipStream_t)stream));
-        src += width;
-        width /= 2;
-    }
-    return PMX_OK;
+    return merkle_levels_dev(ctx, d_nodes, n_trees, total, stream);
 }
 
 extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint64_t *nodes,
@@ -972,40 +993,9 @@ extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size
     PMX_ABI_BEGIN("pmx_merkle_2to1_forest")
     if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest: null pointer");
     size_t total = 0, n_nodes = 0;
-    int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes);
-    if (rc) return rc;
+    if (int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes)) return rc;
     PMX_BIND(ctx);
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d, leaves, total * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pmx_merkle_2to1_forest_dev(ctx, (uint64_t *)d, n_trees, leaves_per_tree, ctx->stream))) return rc;
-    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (roots) PMX_HIP(hipMemcpyAsync(roots, (uint64_t *)d + (n_nodes - n_trees) * 4, n_trees * 32, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
-    PMX_ABI_END
-}
-
-extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint64_t *nodes, uint64_t *root) {
-    PMX_ABI_BEGIN("pmx_merkle_2to1")
-    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1: null pointer");
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    const size_t n_nodes = 2 * n_leaves - 1;
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d, leaves, n_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pmx_merkle_2to1_dev(ctx, (uint64_t *)d, n_leaves, ctx->stream))) return rc;
-    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (root) PMX_HIP(hipMemcpyAsync(root, (uint64_t *)d + (n_nodes - 1) * 4, 32, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
+    return merkle_host(ctx, leaves, n_trees, total, n_nodes, nodes, roots);
     PMX_ABI_END
 }
 

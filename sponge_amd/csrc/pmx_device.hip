@@ -972,7 +972,6 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
 template <class Engine>
 struct Launch {
     static int grid(size_t n) { return (int)((n + Engine::kUnits - 1) / Engine::kUnits); }
-    static size_t lds(const DevConfig &c, uint32_t t) { return Engine::lds_bytes(c, t); }
     // more than 64 KiB of dynamic LDS has to be asked for per kernel (and device)
     template <class K>
     static void allow_lds(K kernel, size_t bytes) {
@@ -998,23 +997,37 @@ struct Launch {
                            c.consts, in, out, n);
         return hipGetLastError();
     }
+    // absorb / squeeze: per-lane kernels, or - on an engine whose permutation must stay wave-uniform - passes on its permutation
+    // (pmx_sponge_plan.hpp).  Only the form the engine has is instantiated.
+    template <class Rows>
+    static hipError_t absorb_rows(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
+                                  const Rows &rows, size_t n, hipStream_t st, const PassScratch &scratch) {
+        if constexpr (Engine::kWaveUniformOnly) {
+            uint64_t *io = const_cast<uint64_t *>(in);   // (the absorb form of the pass kernels only reads `io`)
+            return sponge_passes<false>(c, t, states, tag, index, io, rows, n, st, scratch);
+        } else {
+            hipLaunchKernelGGL((absorb_kernel<Engine, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                               c.consts, states, tag, index, in, rows, n);
+            return hipGetLastError();
+        }
+    }
     static hipError_t absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
-                             const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch & = PassScratch{}) {
-        hipLaunchKernelGGL((absorb_kernel<Engine, RowsFixed>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, states, tag, index, in, RowsFixed{in_len}, n);
-        return hipGetLastError();
+                             const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch) {
+        return absorb_rows(c, t, states, tag, index, in, RowsFixed{in_len}, n, st, scratch);
     }
     static hipError_t absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
-                                    const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch & = PassScratch{}) {
-        hipLaunchKernelGGL((absorb_kernel<Engine, RowsRagged>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, states, tag, index, in, RowsRagged{in, offsets, (uint32_t)max_len}, n);
-        return hipGetLastError();
+                                    const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch &scratch) {
+        return absorb_rows(c, t, states, tag, index, in, RowsRagged{in, offsets, (uint32_t)max_len}, n, st, scratch);
     }
     static hipError_t squeeze(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
-                              uint64_t *out, size_t out_len, size_t n, hipStream_t st, const PassScratch & = PassScratch{}) {
-        hipLaunchKernelGGL(squeeze_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, states, tag, index, out, out_len, n);
-        return hipGetLastError();
+                              uint64_t *out, size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch) {
+        if constexpr (Engine::kWaveUniformOnly) {
+            return sponge_passes<true>(c, t, states, tag, index, out, RowsFixed{out_len}, n, st, scratch);
+        } else {
+            hipLaunchKernelGGL(squeeze_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                               c.consts, states, tag, index, out, out_len, n);
+            return hipGetLastError();
+        }
     }
     // the whole absorb / squeeze call as passes (pmx_sponge_plan.hpp): pass 0 over the batch, then one launch per further
     // permutation a sponge of the batch can need.  The two lists and the per-pass counters live in scratch the caller's
@@ -1030,11 +1043,12 @@ struct Launch {
         allow_lds(permute_listed_kernel<Engine, SQUEEZE, Rows>, Engine::lds_bytes(c, t));
         allow_lds(sponge_first_kernel<Engine, SQUEEZE, Rows>, Engine::lds_bytes(c, t));
         const uint32_t last = (uint32_t)(passes - 1);    // (no sponge permutes in the last pass)
+        const size_t launches = pass_launches(passes);
         uint32_t *scratch = nullptr;                     // [counters, padded to 64 words | list A: n | list B: n]
         const size_t head = (passes + 63) / 64 * 64;
         hipError_t e = hipSuccess;
         uint32_t *lists[2] = {nullptr, nullptr};
-        if (last > 1) {                                  // a second permutation is possible: its sponges travel on a list
+        if (launches > 1) {                              // a second permutation is possible: its sponges travel on a list
             // (NOT hipMallocAsync / hipFreeAsync: with several contexts - several streams - alive, ROCm 7.0's stream-ordered pool
             // handed out blocks whose earlier use was still in flight; tools/soak.py lost sponges and took a memory fault that way)
             e = provider.get(provider.owner, st, (head + 2 * n) * 4, &scratch);
@@ -1049,7 +1063,7 @@ struct Launch {
                                states, tag, index, io, rows, n, last, lists[1], scratch ? scratch + 1 : nullptr);
             e = hipGetLastError();
         }
-        for (uint32_t p = 1; p < last && e == hipSuccess; ++p) {
+        for (uint32_t p = 1; p < launches && e == hipSuccess; ++p) {
             hipLaunchKernelGGL((permute_listed_kernel<Engine, SQUEEZE, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
                                c.consts, states, tag, index, io, rows, p, last, lists[p & 1], scratch + p, lists[(p + 1) & 1], scratch + p + 1);
             e = hipGetLastError();
@@ -1058,15 +1072,33 @@ struct Launch {
         return e;
     }
     // what a launch of `op` would run on (pmx_ctx_engine_info): filled by the engine, completed per kernel family here
-    static hipError_t describe(const DevConfig &c, uint32_t t, int op, size_t len, EngineInfo *o) {
+    static void describe(const DevConfig &c, uint32_t t, int op, size_t len, EngineInfo *o) {
         Engine::describe(*o);
         const bool driver = op == PMX_OP_ABSORB || op == PMX_OP_SQUEEZE;
-        o->waves_per_simd = driver ? Engine::kMinWavesDriver : Engine::kMinWaves;
+        const bool passes = driver && Engine::kWaveUniformOnly;   // a pass is the permutation engine's launch
+        o->waves_per_simd = driver && !passes ? Engine::kMinWavesDriver : Engine::kMinWaves;
         o->lds_bytes = (uint32_t)Engine::lds_bytes(c, t);
         o->launches = 1;
-        return hipSuccess;
+        if (passes) {
+            const size_t passes_z = op == PMX_OP_SQUEEZE ? squeeze_passes(len, c.rounds.rate) : absorb_passes(len, c.rounds.rate);
+            o->launches = (int)pass_launches(passes_z > 0x7fffffff ? 0x7fffffff : passes_z);
+            std::snprintf(o->engine + std::strlen(o->engine), sizeof o->engine - std::strlen(o->engine), " x passes");
+        }
     }
 };
+
+// the table of an engine instantiation (pmx_launch.hpp: EngineOps); taking the address of a launcher instantiates its kernels
+template <class Engine>
+static const EngineOps &engine_ops() {
+    using L = Launch<Engine>;
+    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::absorb, &L::absorb_varlen, &L::squeeze, &Engine::lds_bytes, &L::describe};
+    return ops;
+}
+
+// ---- window engines: four translation units (they dominate the build time, so they compile in parallel), the exponent (1, 3: alpha = 5;
+// 2, 4: any other, ALPHA = 0) x the widths (1, 2: t = 3 .. 6; 3, 4: t = 7 .. 9).  Each exports the lookup of its own half:
+template <int ALPHA, bool WIDE>
+const EngineOps *window_ops(uint32_t t);   // nullptr for a width the translation unit does not hold
 
 #if PMX_TU == 99
 // ---- tuning aid (Makefile target asm1): ONE kernel of one window engine, for reading its ISA and register report in seconds ----------
@@ -1081,120 +1113,23 @@ hipError_t one_ragged(const DevConfig &c, uint64_t *s, uint32_t *tg, uint32_t *i
 #endif
 #elif PMX_TU != 0
 // ---- window engines of this translation unit ------------------------------------------------------------------------
-// four translation units (they dominate the build time, so they compile in parallel): the exponent (1, 3: alpha = 5; 2, 4: any other) x the
-// widths (1, 2: t = 3 .. 6; 3, 4: t = 7 .. 9).  The public launchers of TU 0 pick the half by t, after they have checked that the config
-// has the engine's tables (DevConfig::mfma_dense) and that its LDS fits the device.
-#if PMX_TU == 1 || PMX_TU == 3
-#define PMX_HYB_ALPHA 5
-#else
-#define PMX_HYB_ALPHA 0
-#endif
-#if PMX_TU == 1
-#define PMX_HYB_NAME(op) hybrid5n_##op
-#elif PMX_TU == 3
-#define PMX_HYB_NAME(op) hybrid5w_##op
-#elif PMX_TU == 2
-#define PMX_HYB_NAME(op) hybridgn_##op
-#else
-#define PMX_HYB_NAME(op) hybridgw_##op
-#endif
-#if PMX_TU == 1 || PMX_TU == 2
-#define PMX_HYB_DISPATCH(CALL)                                             \
-    switch (t) {                                                           \
-        case 3: return Launch<HybridEngine<3, PMX_HYB_ALPHA>>::CALL;       \
-        case 4: return Launch<HybridEngine<4, PMX_HYB_ALPHA>>::CALL;       \
-        case 5: return Launch<HybridEngine<5, PMX_HYB_ALPHA>>::CALL;       \
-        case 6: return Launch<HybridEngine<6, PMX_HYB_ALPHA>>::CALL;       \
-        default: return hipErrorInvalidValue;                              \
-    }
-#else
-#define PMX_HYB_DISPATCH(CALL)                                             \
-    switch (t) {                                                           \
-        case 7: return Launch<HybridEngine<7, PMX_HYB_ALPHA>>::CALL;       \
-        case 8: return Launch<HybridEngine<8, PMX_HYB_ALPHA>>::CALL;       \
-        case 9: return Launch<HybridEngine<9, PMX_HYB_ALPHA>>::CALL;       \
-        default: return hipErrorInvalidValue;                              \
-    }
-#endif
-hipError_t PMX_HYB_NAME(permute)(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st) { PMX_HYB_DISPATCH(permute(c, t, states, n, st)); }
-hipError_t PMX_HYB_NAME(hash)(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len,
-                              size_t n, hipStream_t st) {
-    PMX_HYB_DISPATCH(hash(c, t, in, in_len, out, out_len, n, st));
-}
-hipError_t PMX_HYB_NAME(compress)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
-    PMX_HYB_DISPATCH(compress(c, t, in, out, n, st));
-}
-// absorb / squeeze run as passes on the permutation engine of the width (pmx_sponge_plan.hpp)
-hipError_t PMX_HYB_NAME(absorb)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
-                                const uint64_t *in, size_t len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    uint64_t *io = const_cast<uint64_t *>(in);   // (the absorb form of the pass kernel only reads `io`)
-    PMX_HYB_DISPATCH(template sponge_passes<false>(c, t, states, tag, index, io, RowsFixed{len}, n, st, scratch));
-}
-hipError_t PMX_HYB_NAME(absorb_varlen)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
-                                       const uint64_t *in, const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st,
-                                       const PassScratch &scratch) {
-    uint64_t *io = const_cast<uint64_t *>(in);
-    PMX_HYB_DISPATCH(template sponge_passes<false>(c, t, states, tag, index, io, RowsRagged{in, offsets, (uint32_t)max_len}, n, st, scratch));
-}
-hipError_t PMX_HYB_NAME(squeeze)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
-                                 uint64_t *out, size_t len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    PMX_HYB_DISPATCH(template sponge_passes<true>(c, t, states, tag, index, out, RowsFixed{len}, n, st, scratch));
-}
-// LDS one workgroup of the width's engine asks for (the launchers of TU 0 compare it with the device's limit)
-size_t PMX_HYB_NAME(lds_bytes)(const DevConfig &c, uint32_t t) { PMX_HYB_DISPATCH(lds(c, t)); }
-// pmx_ctx_engine_info for the window engines
-hipError_t PMX_HYB_NAME(describe)(const DevConfig &c, uint32_t t, int op, size_t len, EngineInfo *o) {
-    const bool passes = op == PMX_OP_ABSORB || op == PMX_OP_SQUEEZE;
-    const int op_engine = passes ? PMX_OP_PERMUTE : op;        // a pass is the permutation engine's launch
-    auto plain = [&]() -> hipError_t { PMX_HYB_DISPATCH(describe(c, t, op_engine, len, o)); };
-    const hipError_t e = plain();
-    if (e == hipSuccess && passes) {
-        const size_t passes_z = op == PMX_OP_SQUEEZE ? squeeze_passes(len, c.rounds.rate) : absorb_passes(len, c.rounds.rate);
-        const int n_passes = passes_z > 0x7fffffff ? 0x7fffffff : (int)passes_z;
-        o->launches = n_passes > 1 ? n_passes - 1 : n_passes;  // one launch per permutation a sponge of the batch can need
-        std::snprintf(o->engine + std::strlen(o->engine), sizeof o->engine - std::strlen(o->engine), " x passes");
-    }
-    return e;
+constexpr int kTuAlpha = (PMX_TU == 1 || PMX_TU == 3) ? 5 : 0;
+constexpr bool kTuWide = PMX_TU >= 3;
+template <>
+const EngineOps *window_ops<kTuAlpha, kTuWide>(uint32_t t) {
+    const EngineOps *ops = nullptr;
+    static_for<(kTuWide ? 7 : 3), (kTuWide ? 10 : 7)>([&](auto width) {
+        if (t == (uint32_t)width) ops = &engine_ops<HybridEngine<decltype(width)::value, kTuAlpha>>();
+    });
+    return ops;
 }
 
 #else  // PMX_TU == 0
 // ---- public launchers -------------------------------------------------------------------------------------------------
-#define PMX_HYB_DECL(P)                                                                                                          \
-    hipError_t P##permute(const DevConfig &, uint32_t, uint64_t *, size_t, hipStream_t);                                         \
-    hipError_t P##hash(const DevConfig &, uint32_t, const uint64_t *, size_t, uint64_t *, size_t, size_t, hipStream_t);          \
-    hipError_t P##compress(const DevConfig &, uint32_t, const uint64_t *, uint64_t *, size_t, hipStream_t);                      \
-    hipError_t P##absorb(const DevConfig &, uint32_t, uint64_t *, uint32_t *, uint32_t *, const uint64_t *, size_t, size_t, hipStream_t, const PassScratch &); \
-    hipError_t P##squeeze(const DevConfig &, uint32_t, uint64_t *, uint32_t *, uint32_t *, uint64_t *, size_t, size_t, hipStream_t, const PassScratch &); \
-    hipError_t P##absorb_varlen(const DevConfig &, uint32_t, uint64_t *, uint32_t *, uint32_t *, const uint64_t *, const uint64_t *, size_t, size_t, \
-                                hipStream_t, const PassScratch &);                                                               \
-    size_t P##lds_bytes(const DevConfig &, uint32_t);                                                                            \
-    hipError_t P##describe(const DevConfig &, uint32_t, int, size_t, EngineInfo *);
-PMX_HYB_DECL(hybrid5n_)
-PMX_HYB_DECL(hybrid5w_)
-PMX_HYB_DECL(hybridgn_)
-PMX_HYB_DECL(hybridgw_)
-
-// Engine choice (three engines, one per regime):
-//   QuadEngine     t = 3, at most 32768 units: one state per quad of lanes - the call is one permutation's latency
-//   HybridEngine   t = 3 .. 9, configs that have the window tables (DevConfig::mfma_dense: the optimised schedule exists, at least two
-//                  full rounds, the window algebra meets no zero - every config of the reference's tables, any modulus): alpha = 5
-//                  specialised, any other exponent on the generic S-box; absorb / squeeze as passes
-//   LdsEngine      everything else (t = 2, t >= 10, no partial section, a zero in the algebra): run-time width, the reference's dense schedule
-// alpha 5 and 17 have dedicated addition chains in the quad and run-time-width engines, other exponents share the generic S-box.
-static bool window_engine(const DevConfig &c, uint32_t t) {
-    if (!c.has_opt || !c.mfma_dense || t < (uint32_t)PMX_MFMA_MIN_T || t > (uint32_t)PMX_MFMA_MAX_T) return false;
-    const size_t lds = c.rounds.alpha == 5 ? (t <= 6 ? hybrid5n_lds_bytes(c, t) : hybrid5w_lds_bytes(c, t)) : (t <= 6 ? hybridgn_lds_bytes(c, t) : hybridgw_lds_bytes(c, t));
-    return lds <= (size_t)c.max_lds_bytes;
-}
-// the window engine of a width: the exponent's half of the family, then the width's
-#define PMX_WINDOW(CALL) (c.rounds.alpha == 5 ? (t <= 6 ? hybrid5n_##CALL : hybrid5w_##CALL) : (t <= 6 ? hybridgn_##CALL : hybridgw_##CALL))
-// the quad or run-time-width engine of the config's exponent
-#define PMX_BY_ALPHA(ENGINE, CALL)                                           \
-    do {                                                                     \
-        if (c.rounds.alpha == 5) return Launch<ENGINE<5>>::CALL;             \
-        if (c.rounds.alpha == 17) return Launch<ENGINE<17>>::CALL;           \
-        return Launch<ENGINE<0>>::CALL;                                      \
-    } while (0)
+template <> const EngineOps *window_ops<5, false>(uint32_t t);
+template <> const EngineOps *window_ops<5, true>(uint32_t t);
+template <> const EngineOps *window_ops<0, false>(uint32_t t);
+template <> const EngineOps *window_ops<0, true>(uint32_t t);
 
 // the quad engine's table exists (t = 3, optimised schedule) and fits LDS; the lane of each element is fixed by the
 // split only where elements are addressed through capacity / rate (quad_shape below)
@@ -1208,41 +1143,67 @@ static bool quad_shape(const DevConfig &c, uint32_t t) { return quad_table(c, t)
 // chip better - profiles/r05/v_ab_t3_engine_threshold_32769.txt, w_ab_quad_kernels_up_to_16384_only_not_kept.txt).
 static constexpr size_t kQuadMaxUnits = 32768;
 
+// the window engine of the config and width (the exponent's half of the family, then the width's), if the config has its tables and
+// its LDS fits the device
+static const EngineOps *window_engine(const DevConfig &c, uint32_t t) {
+    if (!c.has_opt || !c.mfma_dense || t < (uint32_t)PMX_MFMA_MIN_T || t > (uint32_t)PMX_MFMA_MAX_T) return nullptr;
+    const EngineOps *w = c.rounds.alpha == 5 ? (t <= 6 ? window_ops<5, false>(t) : window_ops<5, true>(t))
+                                             : (t <= 6 ? window_ops<0, false>(t) : window_ops<0, true>(t));
+    return w && w->lds_bytes(c, t) <= (size_t)c.max_lds_bytes ? w : nullptr;
+}
+// the quad or run-time-width engine of the config's exponent
+template <template <int> class Engine>
+static const EngineOps *by_alpha(const DevConfig &c) {
+    return c.rounds.alpha == 5 ? &engine_ops<Engine<5>>() : c.rounds.alpha == 17 ? &engine_ops<Engine<17>>() : &engine_ops<Engine<0>>();
+}
+
+// Engine choice (three engines, one per regime):
+//   QuadEngine     t = 3, at most 32768 units: one state per quad of lanes - the call is one permutation's latency
+//   HybridEngine   t = 3 .. 9, configs that have the window tables (DevConfig::mfma_dense: the optimised schedule exists, at least two
+//                  full rounds, the window algebra meets no zero - every config of the reference's tables, any modulus): alpha = 5
+//                  specialised, any other exponent on the generic S-box; absorb / squeeze as passes
+//   LdsEngine      everything else (t = 2, t >= 10, no partial section, a zero in the algebra): run-time width, the reference's dense schedule
+// alpha 5 and 17 have dedicated addition chains in the quad and run-time-width engines, other exponents share the generic S-box.
+// The ONLY place that decides it: every launcher below and describe_launch (pmx_ctx_engine_info) go through the table returned here.
+// nullptr: `op` is none of PMX_OP_*.
+static const EngineOps *select_engine(const DevConfig &c, uint32_t t, int op, size_t n) {
+    bool quad;
+    switch (op) {
+        case PMX_OP_PERMUTE: quad = quad_table(c, t); break;
+        case PMX_OP_HASH:
+        case PMX_OP_ABSORB:
+        case PMX_OP_SQUEEZE:
+        // (the split (rate 3, capacity 0) of the same width takes the one-lane-per-state engine at every tree level)
+        case PMX_OP_COMPRESS: quad = quad_shape(c, t); break;
+        default: return nullptr;
+    }
+    if (quad && n <= kQuadMaxUnits) return by_alpha<QuadEngine>(c);
+    if (const EngineOps *w = window_engine(c, t)) return w;
+    return by_alpha<LdsEngine>(c);
+}
+
 hipError_t launch_permute(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st) {
-    if (quad_table(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, permute(c, t, states, n, st));
-    if (window_engine(c, t)) return PMX_WINDOW(permute(c, t, states, n, st));
-    PMX_BY_ALPHA(LdsEngine, permute(c, t, states, n, st));
+    return select_engine(c, t, PMX_OP_PERMUTE, n)->permute(c, t, states, n, st);
 }
 hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len,
                        size_t n, hipStream_t st) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, hash(c, t, in, in_len, out, out_len, n, st));
-    if (window_engine(c, t)) return PMX_WINDOW(hash(c, t, in, in_len, out, out_len, n, st));
-    PMX_BY_ALPHA(LdsEngine, hash(c, t, in, in_len, out, out_len, n, st));
+    return select_engine(c, t, PMX_OP_HASH, n)->hash(c, t, in, in_len, out, out_len, n, st);
 }
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
-    // (the split (rate 3, capacity 0) of the same width takes the one-lane-per-state engine at every level)
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, compress(c, t, in, out, n, st));
-    if (window_engine(c, t)) return PMX_WINDOW(compress(c, t, in, out, n, st));
-    PMX_BY_ALPHA(LdsEngine, compress(c, t, in, out, n, st));
+    return select_engine(c, t, PMX_OP_COMPRESS, n)->compress(c, t, in, out, n, st);
 }
 hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, absorb(c, t, states, tag, index, in, in_len, n, st));
-    if (window_engine(c, t)) return PMX_WINDOW(absorb(c, t, states, tag, index, in, in_len, n, st, scratch));
-    PMX_BY_ALPHA(LdsEngine, absorb(c, t, states, tag, index, in, in_len, n, st, scratch));
+    return select_engine(c, t, PMX_OP_ABSORB, n)->absorb(c, t, states, tag, index, in, in_len, n, st, scratch);
 }
 hipError_t launch_squeeze(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                           uint64_t *out, size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, squeeze(c, t, states, tag, index, out, out_len, n, st));
-    if (window_engine(c, t)) return PMX_WINDOW(squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
-    PMX_BY_ALPHA(LdsEngine, squeeze(c, t, states, tag, index, out, out_len, n, st, scratch));
+    return select_engine(c, t, PMX_OP_SQUEEZE, n)->squeeze(c, t, states, tag, index, out, out_len, n, st, scratch);
 }
-// ragged rows: the engine choice of launch_absorb (quad, window engine as passes, run-time width)
+// ragged rows: an absorb like any other to the engine choice
 hipError_t launch_absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
                                 const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch &scratch) {
-    if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st));
-    if (window_engine(c, t)) return PMX_WINDOW(absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch));
-    PMX_BY_ALPHA(LdsEngine, absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch));
+    return select_engine(c, t, PMX_OP_ABSORB, n)->absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch);
 }
 // per row: new; absorb(row); squeeze_native(out_len) = n fresh sponges (Absorbing{0} and a zero state: all-zero words, mod.rs:219-230) in
 // a block of the pass pool, the ragged absorb on them, then the fixed squeeze writing straight into `out`.  (The pass form of the absorb
@@ -1262,25 +1223,14 @@ hipError_t launch_hash_varlen(const DevConfig &c, uint32_t t, const uint64_t *in
     return e;
 }
 
-// ---- pmx_ctx_engine_info: the same conditions, describing instead of launching ------------------------------------------
+// ---- pmx_ctx_engine_info: the engine the launcher of `op` selects, describing instead of launching --------------------------
 hipError_t describe_launch(const DevConfig &c, uint32_t t, int op, size_t n, size_t len, EngineInfo *o) {
     std::memset(o, 0, sizeof *o);
     o->width = (int)t;
-    switch (op) {
-        case PMX_OP_PERMUTE:
-            if (quad_table(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, describe(c, t, op, len, o));
-            break;
-        case PMX_OP_HASH:
-        case PMX_OP_ABSORB:
-        case PMX_OP_SQUEEZE:
-        case PMX_OP_COMPRESS:
-            if (quad_shape(c, t) && n <= kQuadMaxUnits) PMX_BY_ALPHA(QuadEngine, describe(c, t, op, len, o));
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    if (window_engine(c, t)) return PMX_WINDOW(describe(c, t, op, len, o));
-    PMX_BY_ALPHA(LdsEngine, describe(c, t, op, len, o));
+    const EngineOps *engine = select_engine(c, t, op, n);
+    if (!engine) return hipErrorInvalidValue;
+    engine->describe(c, t, op, len, o);
+    return hipSuccess;
 }
 
 // ---- authentication paths (pmx_merkle_verify_paths_dev) --------------------------------------------------------------

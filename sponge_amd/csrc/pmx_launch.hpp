@@ -37,6 +37,27 @@ hipError_t launch_absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states
 hipError_t launch_hash_varlen(const DevConfig &c, uint32_t t, const uint64_t *in, const uint64_t *offsets, size_t max_len, uint64_t *out,
                               size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch);
 
+// What ONE engine instantiation serves (pmx_device.hip: engine_ops<Engine>() fills it, select_engine picks the table of a call): every
+// member has the signature of its launch_* above whatever the engine - one that runs absorb / squeeze as per-lane kernels does not touch
+// the PassScratch, one that runs them as passes takes its lists from it.  Both the launchers and describe_launch go through the table
+// select_engine returns, so what pmx_ctx_engine_info reports is what a launch runs.
+// Adding an operation: a member here, its line in engine_ops, a launch_* one-liner.
+struct EngineOps {
+    hipError_t (*permute)(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st);
+    hipError_t (*hash)(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, size_t n,
+                       hipStream_t st);
+    hipError_t (*compress)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
+    hipError_t (*absorb)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
+                         size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch);
+    hipError_t (*absorb_varlen)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
+                                const uint64_t *offsets, size_t max_len, size_t n, hipStream_t st, const PassScratch &scratch);
+    hipError_t (*squeeze)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, uint64_t *out,
+                          size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch);
+    size_t (*lds_bytes)(const DevConfig &c, uint32_t t);   // dynamic LDS one workgroup asks for
+    // fills EngineInfo for `op` (PMX_OP_*) at `len` elements per sponge: the engine's own fields, then waves, LDS and launches of the op
+    void (*describe)(const DevConfig &c, uint32_t t, int op, size_t len, EngineInfo *o);
+};
+
 // Authentication paths, one level per step (pmx_merkle_verify_paths_dev): pairs[i] = (cur[i], sibling) or (sibling, cur[i])
 // by bit `level` of indices[i], sibling = paths[i][level]; then ok[i] = (cur[i] == root) && indices[i] < 2^depth.
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,

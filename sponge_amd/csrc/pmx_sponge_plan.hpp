@@ -43,6 +43,9 @@ constexpr size_t kSpongeMaxLen = 0x7fffffffu;
 // (a sponge permutes at most ceil(len / rate) times in one call - at least once when an absorbing sponge squeezes nothing)
 PMX_FN size_t absorb_passes(size_t len, uint32_t rate) { return len == 0 ? 0 : 1 + (len + rate - 1) / rate; }
 PMX_FN size_t squeeze_passes(size_t len, uint32_t rate) { return len == 0 ? 2 : 1 + (len + rate - 1) / rate; }
+// kernel launches of a call of `passes` passes: one per permutation a sponge of the batch can need - the last pass permutes nothing and
+// runs behind the permutation of the launch before it (the launch loop's own bound and what pmx_ctx_engine_info reports)
+PMX_FN size_t pass_launches(size_t passes) { return passes > 1 ? passes - 1 : passes; }
 
 // Variable-length rows (pmx_*_varlen_batch*): row i of a call is the input elements [offsets[i], offsets[i + 1]), each sponge with
 // a length of its own.  The device does not validate its offsets: a decreasing pair reads as an empty row, and a row is absorbed up to
