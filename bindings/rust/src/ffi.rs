@@ -83,6 +83,15 @@ extern "C" {
                                        d_in: *const u64, in_len: usize, n: usize, stream: *mut c_void) -> c_int;
     pub fn pmx_sponge_squeeze_batch_dev(ctx: *mut pmx_ctx, d_states: *mut u64, d_mode_tag: *mut u32, d_mode_index: *mut u32,
                                         d_out: *mut u64, out_len: usize, n: usize, stream: *mut c_void) -> c_int;
+    // squeeze_bytes / squeeze_bits of n sponges (mod.rs:256-286): out [n][len] bytes, for bits one byte per bit holding 0 or 1 (a Vec<bool>)
+    pub fn pmx_sponge_squeeze_bytes_batch(ctx: *mut pmx_ctx, states: *mut u64, mode_tag: *mut u32, mode_index: *mut u32,
+                                          out: *mut u8, num_bytes: usize, n: usize) -> c_int;
+    pub fn pmx_sponge_squeeze_bytes_batch_dev(ctx: *mut pmx_ctx, d_states: *mut u64, d_mode_tag: *mut u32, d_mode_index: *mut u32,
+                                              d_out: *mut u8, num_bytes: usize, n: usize, stream: *mut c_void) -> c_int;
+    pub fn pmx_sponge_squeeze_bits_batch(ctx: *mut pmx_ctx, states: *mut u64, mode_tag: *mut u32, mode_index: *mut u32,
+                                         out: *mut u8, num_bits: usize, n: usize) -> c_int;
+    pub fn pmx_sponge_squeeze_bits_batch_dev(ctx: *mut pmx_ctx, d_states: *mut u64, d_mode_tag: *mut u32, d_mode_index: *mut u32,
+                                             d_out: *mut u8, num_bits: usize, n: usize, stream: *mut c_void) -> c_int;
     // variable-length rows: row i is input[offsets[i] .. offsets[i + 1]), offsets [n + 1]
     pub fn pmx_hash_varlen_batch(ctx: *mut pmx_ctx, input: *const u64, offsets: *const u64, out: *mut u64, out_len: usize,
                                  n: usize) -> c_int;

@@ -210,6 +210,26 @@ impl<F: PrimeField> BatchPoseidon<F> {
         }
         out
     }
+    /// `squeeze_bytes(num_bytes)` of n sponges held as `states` (len = n*t) and mode words (`PMX_MODE_*`, index), all advanced in
+    /// place as `squeeze_native_field_elements` would; one `Vec<u8>` per sponge.  The bytes are cut from the canonical integers on
+    /// the device (semantics of src/poseidon/mod.rs:256-270): no `into_bigint` pass on the host.
+    pub fn squeeze_bytes(&self, states: &mut [F], mode_tag: &mut [u32], mode_index: &mut [u32], num_bytes: usize) -> Vec<Vec<u8>> {
+        let n = mode_tag.len();
+        assert!(states.len() == n * self.t && mode_index.len() == n, "states / mode words are not those of n sponges");
+        let mut out = vec![0u8; n * num_bytes];
+        check(unsafe { ffi::pmx_sponge_squeeze_bytes_batch(self.ctx.0, limbs_mut(states), mode_tag.as_mut_ptr(), mode_index.as_mut_ptr(),
+                                                           out.as_mut_ptr(), num_bytes, n) });
+        if num_bytes == 0 { vec![Vec::new(); n] } else { out.chunks(num_bytes).map(|r| r.to_vec()).collect() }
+    }
+    /// `squeeze_bits(num_bits)` of n sponges (src/poseidon/mod.rs:272-286); the library writes one byte per bit holding 0 or 1.
+    pub fn squeeze_bits(&self, states: &mut [F], mode_tag: &mut [u32], mode_index: &mut [u32], num_bits: usize) -> Vec<Vec<bool>> {
+        let n = mode_tag.len();
+        assert!(states.len() == n * self.t && mode_index.len() == n, "states / mode words are not those of n sponges");
+        let mut out = vec![0u8; n * num_bits];
+        check(unsafe { ffi::pmx_sponge_squeeze_bits_batch(self.ctx.0, limbs_mut(states), mode_tag.as_mut_ptr(), mode_index.as_mut_ptr(),
+                                                          out.as_mut_ptr(), num_bits, n) });
+        if num_bits == 0 { vec![Vec::new(); n] } else { out.chunks(num_bits).map(|r| r.iter().map(|b| *b != 0).collect()).collect() }
+    }
     /// Authentication paths of `indices` over a node array made by `merkle`: `[k][depth]` siblings, bottom-up.
     pub fn merkle_paths(&self, nodes: &[F], indices: &[u64]) -> Vec<F> {
         let n_leaves = (nodes.len() + 1) / 2;

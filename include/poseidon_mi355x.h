@@ -240,6 +240,38 @@ int pmx_sponge_absorb_varlen_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mod
 int pmx_sponge_absorb_varlen_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
                                        const uint64_t *d_in, const uint64_t *d_offsets, size_t max_len, size_t n, void *stream);
 
+/* ---- squeeze bytes and bits ----------------------------------------------------------------------
+ * CryptographicSponge::squeeze_bytes / squeeze_bits (src/poseidon/mod.rs:256-286) on n sponges held as (state, mode) like the drivers
+ * above.  With B the bit length of the context's modulus (MODULUS_BIT_SIZE; this library takes 2^224 < p < 2^255):
+ * bytes: u = (B - 1) / 8 (28 .. 31), E = ceil(num_bytes / u): squeeze E native elements; each contributes the first u bytes of its
+ *   canonical integer in little-endian order (into_bigint().to_bytes_le()[..u], mod.rs:257-268); the concatenation is truncated to
+ *   num_bytes.  out: [n][num_bytes], rows packed without padding.
+ * bits: u = B - 1 (224 .. 254), E = ceil(num_bits / u), bits little-endian (to_bits_le()[..u], mod.rs:274-285), truncated to num_bits.
+ *   out: [n][num_bits], ONE BYTE PER BIT holding 0 or 1 - the memory of a Rust Vec<bool>, passed as it stands.
+ * States and mode words end exactly as after pmx_sponge_squeeze_batch[_dev] with out_len = E on the same sponges, E = 0 included (that
+ * call still permutes an Absorbing sponge, mod.rs:324-328; so does this one).  Sponges of one call may be in different modes.
+ * The canonical integer comes from the ABI residue by one Montgomery reduction on the device (no host pass over the elements, and only
+ * n * num_bytes bytes cross the link from the host entries).  Squeezed elements are reduced, so the question does not arise here, but
+ * the conversion itself takes any 256-bit word modulo p.
+ * _dev: d_out needs NO alignment (num_bytes may be odd: rows start at any address); states and mode words as for the native _dev squeeze.
+ *   A call writes [d_out, d_out + n * num_bytes) and nothing else of the caller's.  E is subject to the 65536-rate limit of the native
+ *   _dev squeeze (PMX_ERR_ARG beyond, nothing launched).  Only enqueues; the E native elements pass through a scratch block of the
+ *   context's per-stream pool (the provisos of the _dev drivers above hold: not to be captured into a hipGraph).  The block is at most
+ *   PMX_SQUEEZE_SCRATCH_BYTES, or E * 32 bytes if one sponge needs more: a call with n * E * 32 above it runs in slices over sponges.
+ * Host entries: mode words are validated; any length (a call beyond 65536 rates of elements is cut on element boundaries with the rule
+ *   of the native host squeeze: never a last piece of exactly one rate).
+ * To the engine choice this is a PMX_OP_SQUEEZE of E elements: pmx_ctx_engine_info(ctx, PMX_OP_SQUEEZE, n, E) names the engine; its
+ * `launches` does not count the conversion launch (one per slice). */
+#define PMX_SQUEEZE_SCRATCH_BYTES ((size_t)64 << 20)
+int pmx_sponge_squeeze_bytes_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, uint8_t *out,
+                                   size_t num_bytes, size_t n);
+int pmx_sponge_squeeze_bytes_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index, uint8_t *d_out,
+                                       size_t num_bytes, size_t n, void *stream);
+int pmx_sponge_squeeze_bits_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, uint8_t *out,
+                                  size_t num_bits, size_t n);
+int pmx_sponge_squeeze_bits_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index, uint8_t *d_out,
+                                      size_t num_bits, size_t n, void *stream);
+
 /* ---- 2-to-1 Merkle compression ------------------------------------------------------------------
  * parent = (new; absorb([left, right]); squeeze_native(1))[0]  (needs rate >= 2), level by level.
  * leaves: [n_leaves][4], n_leaves a power of two.  nodes (may be NULL): [2*n_leaves-1][4] receives the

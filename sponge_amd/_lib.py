@@ -119,6 +119,12 @@ SIGNATURES = {
                                                    ctypes.c_void_p]),
     "pmx_sponge_squeeze_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, _u64p, _sz, _sz,
                                                     ctypes.c_void_p]),
+    "pmx_sponge_squeeze_bytes_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, ctypes.c_void_p, _sz, _sz]),
+    "pmx_sponge_squeeze_bytes_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, ctypes.c_void_p, _sz, _sz,
+                                                          ctypes.c_void_p]),
+    "pmx_sponge_squeeze_bits_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, ctypes.c_void_p, _sz, _sz]),
+    "pmx_sponge_squeeze_bits_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, ctypes.c_void_p, _sz, _sz,
+                                                         ctypes.c_void_p]),
     "pmx_hash_varlen_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, _sz]),
     "pmx_hash_varlen_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _sz, _u64p, _sz, _sz, ctypes.c_void_p]),
     "pmx_sponge_absorb_varlen_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, _u64p, _u64p, _sz]),
@@ -172,14 +178,17 @@ TEST_HOOK_SIGNATURES = {
 _lib = None
 _path = LIB_PATH
 _hooks = False
+_older = False
 
 
-def use_library(path: str, test_hooks: bool = False) -> None:
-    """Bind another build of the library (tests only: the test-hook build, a coverage build).  Before the first lib()."""
-    global _path, _hooks
+def use_library(path: str, test_hooks: bool = False, older_build: bool = False) -> None:
+    """Bind another build of the library (tests only: the test-hook build, a coverage build).  Before the first lib().
+    older_build: a build of an earlier commit (a benchmark's yardstick, tools/squeeze_bytes_rate.py): entry points it does not export
+    yet are left unbound instead of failing the load; its ABI version must still be this one."""
+    global _path, _hooks, _older
     if _lib is not None and os.path.abspath(path) != os.path.abspath(_path):
         raise RuntimeError("use_library() after another build of the library was loaded")
-    _path, _hooks = path, test_hooks
+    _path, _hooks, _older = path, test_hooks, older_build
 
 
 def use_test_library() -> None:
@@ -206,9 +215,13 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(_path)
         sigs = list(SIGNATURES.items()) + (list(TEST_HOOK_SIGNATURES.items()) if _hooks else [])
         for name, (restype, argtypes) in sigs:
+            if _older and not hasattr(handle, name):
+                continue
             fn = getattr(handle, name)
             fn.restype = restype
             fn.argtypes = argtypes
+        if _older and handle.pmx_abi_version() != ABI_VERSION:
+            raise ImportError(f"{_path}: ABI version {handle.pmx_abi_version()}, this binding is {ABI_VERSION}")
         _lib = handle
     return _lib
 

@@ -20,6 +20,7 @@
 #include "pmx_prepare.hpp"
 #include "pmx_launch.hpp"
 #include "pmx_sponge_plan.hpp"
+#include "pmx_squeeze_cut.hpp"
 
 namespace pmx {
 
@@ -783,6 +784,95 @@ extern "C" int pmx_sponge_absorb_batch(pmx_ctx *ctx, uint64_t *states, uint32_t 
 extern "C" int pmx_sponge_squeeze_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index,
                                         uint64_t *out, size_t out_len, size_t n) {
     return sponge_host(ctx, states, mode_tag, mode_index, nullptr, out, out_len, n, false);
+}
+
+// ---- squeeze bytes and bits ------------------------------------------------------------------------
+// squeeze_bytes / squeeze_bits (mod.rs:256-286): `len` output units (bytes, or bits stored a byte each) per sponge come from
+// cut_elems(len, unit) native elements (pmx_squeeze_cut.hpp); to the pass limit and the engine choice the call is that native squeeze.
+static int squeeze_cut_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_tag, uint32_t *d_index, uint8_t *d_out, size_t len, size_t n,
+                           void *stream, bool bits, const char *who) {
+    if (!ctx || ((!d_states || !d_tag || !d_index) && n) || (!d_out && n && len)) return set_error(PMX_ERR_ARG, "%s: null pointer", who);
+    if (n == 0) return PMX_OK;
+    if (int rc = dev_batch_args(d_states, nullptr, n)) return rc;
+    if (len && n > SIZE_MAX / len) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    const size_t elems = cut_elems(len, cut_unit(ctx->dev.field, bits));
+    if (elems > kSpongeMaxLen) return set_error(PMX_ERR_ARG, "%s: %zu elements per sponge is too large", who, elems);   // (the plan's 32-bit arithmetic)
+    if (int rc = check_pass_count(ctx, PMX_OP_SQUEEZE, n, elems, who)) return rc;
+    size_t elem_bytes = 0;   // only its overflow check is wanted: the launcher indexes n * elems elements with size_t
+    if (int rc = batch_bytes(n, elems, &elem_bytes)) return rc;
+    PMX_ABI_BEGIN(who)
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->pass_lock);
+    PMX_HIP(launch_squeeze_cut(ctx->dev, ctx->t, d_states, d_tag, d_index, d_out, len, bits, n, (hipStream_t)stream, ctx_passes(ctx)));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+extern "C" int pmx_sponge_squeeze_bytes_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
+                                                  uint8_t *d_out, size_t num_bytes, size_t n, void *stream) {
+    return squeeze_cut_dev(ctx, d_states, d_mode_tag, d_mode_index, d_out, num_bytes, n, stream, false, "pmx_sponge_squeeze_bytes_batch_dev");
+}
+
+extern "C" int pmx_sponge_squeeze_bits_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index,
+                                                 uint8_t *d_out, size_t num_bits, size_t n, void *stream) {
+    return squeeze_cut_dev(ctx, d_states, d_mode_tag, d_mode_index, d_out, num_bits, n, stream, true, "pmx_sponge_squeeze_bits_batch_dev");
+}
+
+// Host buffers: states and mode words go up once and stay on the device; a call beyond kMaxPasses rates of elements is cut on element
+// boundaries with the rule of sponge_host (never a last piece of exactly one rate, mod.rs:175), the truncation falls into the last piece,
+// and every piece's [n][piece] block comes down into its columns of the caller's rows: n * len bytes over the link in all.
+static int squeeze_cut_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *index, uint8_t *out, size_t len, size_t n, bool bits,
+                            const char *who) {
+    PMX_ABI_BEGIN(who)
+    if (!ctx || ((!states || !tag || !index) && n)) return set_error(PMX_ERR_ARG, "%s: null pointer", who);
+    if (n == 0) return PMX_OK;
+    if (!out && len) return set_error(PMX_ERR_ARG, "%s: null data pointer", who);
+    if (len && n > SIZE_MAX / len) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    int rc = check_modes(ctx, tag, index, n);
+    if (rc) return rc;
+    const size_t unit = cut_unit(ctx->dev.field, bits), elems = cut_elems(len, (uint32_t)unit);
+    const size_t rate = ctx->dev.rounds.rate, max_elems = kMaxPasses * rate;
+    size_t st_bytes = 0, piece_bytes = 0;
+    if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(n, std::min(elems, max_elems), &piece_bytes))) return rc;
+    const size_t widest = std::min(len, max_elems * unit);   // output units of the longest piece
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    void *d_st = nullptr, *d_io = nullptr, *d_tag = nullptr, *d_idx = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, st_bytes, &d_st))) return rc;
+    if ((rc = ctx_scratch(ctx, 1, n * widest, &d_io))) return rc;
+    if ((rc = ctx_scratch(ctx, 2, n * 4, &d_tag))) return rc;
+    if ((rc = ctx_scratch(ctx, 3, n * 4, &d_idx))) return rc;
+    StreamDrain drain{ctx};
+    hipStream_t st = ctx->stream;
+    PMX_HIP(hipMemcpyAsync(d_st, states, st_bytes, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(d_tag, tag, n * 4, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(d_idx, index, n * 4, hipMemcpyHostToDevice, st));
+    size_t done = 0;   // elements squeezed so far
+    do {
+        size_t piece = elems - done < max_elems ? elems - done : max_elems;
+        if (elems - done - piece == rate) piece -= rate;   // (kMaxPasses > 1: the piece stays positive and is not `rate` itself)
+        const size_t col = done * unit, width = std::min(len - col, piece * unit);
+        if ((rc = squeeze_cut_dev(ctx, (uint64_t *)d_st, (uint32_t *)d_tag, (uint32_t *)d_idx, (uint8_t *)d_io, width, n, st, bits, who))) return rc;
+        if (width == len && len) PMX_HIP(hipMemcpyAsync(out, d_io, n * len, hipMemcpyDeviceToHost, st));
+        else if (width) PMX_HIP(hipMemcpy2DAsync(out + col, len, d_io, width, width, n, hipMemcpyDeviceToHost, st));
+        done += piece;
+    } while (done < elems);
+    PMX_HIP(hipMemcpyAsync(states, d_st, st_bytes, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(tag, d_tag, n * 4, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(index, d_idx, n * 4, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+extern "C" int pmx_sponge_squeeze_bytes_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, uint8_t *out,
+                                              size_t num_bytes, size_t n) {
+    return squeeze_cut_host(ctx, states, mode_tag, mode_index, out, num_bytes, n, false, "pmx_sponge_squeeze_bytes_batch");
+}
+
+extern "C" int pmx_sponge_squeeze_bits_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, uint8_t *out,
+                                             size_t num_bits, size_t n) {
+    return squeeze_cut_host(ctx, states, mode_tag, mode_index, out, num_bits, n, true, "pmx_sponge_squeeze_bits_batch");
 }
 
 // ---- variable-length rows ------------------------------------------------------------------------

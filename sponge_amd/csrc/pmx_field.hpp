@@ -576,6 +576,50 @@ PMX_FN Abi abi_add_mod(const Abi &a, const Abi &b, const uint32_t *p32) {
     return r;
 }
 
+// ABI residue a = x * 2^256 mod p  ->  the canonical integer x in [0, p) as 8 x 32-bit words: ark-ff's into_bigint, what
+// squeeze_bytes / squeeze_bits cut into bytes and bits (src/poseidon/mod.rs:256-286).  In the 9 x 29-bit domain
+// x = (a * 2^5) * 2^-261: the product by 2^5 is a shift of the limbs, so the nine reduction steps alone remain (81 multiplies, no
+// operand products).  Needs p, pinv and the p32 words of `io`.
+// Any a < 2^256 is accepted, reduced or not: T = a * 2^5 < 2^261 and m < 2^261 give (T + m p) / 2^261 < p + 1, i.e. a value in
+// [0, p] congruent to x - p itself only for an unreduced multiple of p -, so ONE conditional subtraction makes it canonical.
+PMX_FN Abi abi_to_canonical(const Abi &a, const FieldRt &f) {
+    const Fe s = limbs_32_to_29(a);   // top limb < 2^24
+    Fe t;
+#pragma unroll
+    for (int i = 0; i < kN; ++i) t.l[i] = ((s.l[i] << 5) | (i ? s.l[i - 1] >> (kW - 5) : 0u)) & kMask;
+    uint32_t m[kN];
+    Fe out;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * kN - 1; ++k) {
+        const int lo_j = k < kN ? 0 : k - (kN - 1);
+        const int hi_j = k < kN ? k - 1 : kN - 1;   // m_k itself enters through mont_step
+        if (k < kN) acc += t.l[k];
+#pragma unroll
+        for (int j = lo_j; j <= hi_j; ++j) acc += (uint64_t)m[j] * f.p[k - j];
+        if (k < kN) {
+            m[k] = mont_step(acc, f);
+        } else {
+            out.l[k - kN] = (uint32_t)acc & kMask;
+            acc >>= kW;
+        }
+    }
+    out.l[kN - 1] = (uint32_t)acc;   // value <= p < 2^255: norm
+    const Abi v = limbs_29_to_32(out);
+    uint32_t d[8];
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint64_t w = (uint64_t)v.w[i] - f.io[kIoP32 + i] - borrow;
+        d[i] = (uint32_t)w;
+        borrow = (uint32_t)(w >> 32) & 1u;
+    }
+    Abi r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.w[i] = borrow ? v.w[i] : d[i];
+    return r;
+}
+
 #if defined(__HIPCC__)
 // 32-byte ABI element <-> two 16-byte vectors
 __device__ __forceinline__ Abi abi_from_u4(const uint4 &lo, const uint4 &hi) {

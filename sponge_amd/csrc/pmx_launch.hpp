@@ -37,6 +37,14 @@ hipError_t launch_absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states
 hipError_t launch_hash_varlen(const DevConfig &c, uint32_t t, const uint64_t *in, const uint64_t *offsets, size_t max_len, uint64_t *out,
                               size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch);
 
+// squeeze_bytes (bits = false) / squeeze_bits (mod.rs:256-286) of n sponges into out [n][len], one byte per output unit (pmx_convert.hip):
+// launch_squeeze of ceil(len / unit) native elements into a block of `scratch`, then the conversion kernel from it into `out`; states and
+// mode words end as after that native squeeze.  `out` needs no alignment.  Scratch is bounded by kCutScratchBytes: a larger call runs in
+// slices over sponges through one block.
+constexpr size_t kCutScratchBytes = PMX_SQUEEZE_SCRATCH_BYTES;
+hipError_t launch_squeeze_cut(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, uint8_t *out, size_t len,
+                              bool bits, size_t n, hipStream_t st, const PassScratch &scratch);
+
 // What ONE engine instantiation serves (pmx_device.hip: engine_ops<Engine>() fills it, select_engine picks the table of a call): every
 // member has the signature of its launch_* above whatever the engine - one that runs absorb / squeeze as per-lane kernels does not touch
 // the PassScratch, one that runs them as passes takes its lists from it.  Both the launchers and describe_launch go through the table

@@ -290,6 +290,24 @@ public:
                                        out.empty() ? dummy.l.data() : out[0].l.data(), num_elements, n_));
         return out;
     }
+    // squeeze_bytes of every sponge (mod.rs:256-270): [n][num_bytes], cut from the canonical integers on the device
+    std::vector<uint8_t> squeeze_bytes(size_t num_bytes) {
+        std::vector<uint8_t> out(n_ * num_bytes);
+        if (n_ == 0) return out;
+        uint8_t dummy = 0;
+        check(pmx_sponge_squeeze_bytes_batch(parameters.context(device_)->get(), state[0].l.data(), mode_tag.data(), mode_index.data(),
+                                             out.empty() ? &dummy : out.data(), num_bytes, n_));
+        return out;
+    }
+    // squeeze_bits of every sponge (mod.rs:272-286): [n][num_bits], one byte per bit holding 0 or 1
+    std::vector<uint8_t> squeeze_bits(size_t num_bits) {
+        std::vector<uint8_t> out(n_ * num_bits);
+        if (n_ == 0) return out;
+        uint8_t dummy = 0;
+        check(pmx_sponge_squeeze_bits_batch(parameters.context(device_)->get(), state[0].l.data(), mode_tag.data(), mode_index.data(),
+                                            out.empty() ? &dummy : out.data(), num_bits, n_));
+        return out;
+    }
 
 private:
     BatchPoseidonSponge(PoseidonConfig p, std::vector<Fp> st, std::vector<uint32_t> tag, std::vector<uint32_t> idx, size_t n, int dev)

@@ -244,6 +244,22 @@ class Context:
                                                        out_len, n))
         return out
 
+    def sponge_squeeze_bytes_batch(self, states, tag, index, num_bytes: int) -> np.ndarray:
+        """squeeze_bytes (mod.rs:256-270) of every sponge: [n][num_bytes] uint8; states / tag / index in place."""
+        n = tag.shape[0]
+        out = np.zeros((n, num_bytes), dtype=np.uint8)
+        _lib.check(_lib.lib().pmx_sponge_squeeze_bytes_batch(self._h, _ptr(states), _ptr(tag), _ptr(index),
+                                                             _ptr(out) if out.size else None, num_bytes, n))
+        return out
+
+    def sponge_squeeze_bits_batch(self, states, tag, index, num_bits: int) -> np.ndarray:
+        """squeeze_bits (mod.rs:272-286) of every sponge: [n][num_bits] bool (one byte per bit, as the library writes them)."""
+        n = tag.shape[0]
+        out = np.zeros((n, num_bits), dtype=np.uint8)
+        _lib.check(_lib.lib().pmx_sponge_squeeze_bits_batch(self._h, _ptr(states), _ptr(tag), _ptr(index),
+                                                            _ptr(out) if out.size else None, num_bits, n))
+        return out.view(np.bool_)
+
     def hash_varlen_batch(self, elems, offsets=None, out_len: int = 1) -> np.ndarray:
         """Per row i: new; absorb(elems[offsets[i] .. offsets[i+1]]); squeeze_native(out_len) (pmx_hash_varlen_batch).  `elems` is
         [*][4] with `offsets` [n+1], or a list of [L_i][4] arrays (offsets None).  Returns [n][out_len][4]."""
@@ -294,6 +310,14 @@ class Context:
 
     def sponge_squeeze_batch_dev(self, d_states, d_tag, d_index, d_out, out_len, n, stream=0) -> None:
         _lib.check(_lib.lib().pmx_sponge_squeeze_batch_dev(self._h, d_states, d_tag, d_index, d_out, out_len, n, stream))
+
+    def sponge_squeeze_bytes_batch_dev(self, d_states, d_tag, d_index, d_out, num_bytes, n, stream=0) -> None:
+        """d_out: [n][num_bytes] bytes at any address."""
+        _lib.check(_lib.lib().pmx_sponge_squeeze_bytes_batch_dev(self._h, d_states, d_tag, d_index, d_out, num_bytes, n, stream))
+
+    def sponge_squeeze_bits_batch_dev(self, d_states, d_tag, d_index, d_out, num_bits, n, stream=0) -> None:
+        """d_out: [n][num_bits] bytes holding 0 or 1, at any address."""
+        _lib.check(_lib.lib().pmx_sponge_squeeze_bits_batch_dev(self._h, d_states, d_tag, d_index, d_out, num_bits, n, stream))
 
     def hash_varlen_batch_dev(self, d_in, d_offsets, max_len: int, d_out, out_len: int, n: int, stream=0) -> None:
         """d_offsets: [n+1] u64 on the device, not validated; max_len bounds every row (a longer one is absorbed up to max_len)."""
@@ -349,6 +373,14 @@ class BatchPoseidonSponge:
         """[n][num_elements][4]  (mod.rs:321-341)."""
         return self.parameters.context(self.device).sponge_squeeze_batch(self.state, self.mode_tag, self.mode_index,
                                                                         num_elements)
+
+    def squeeze_bytes(self, num_bytes: int) -> np.ndarray:
+        """[n][num_bytes] uint8: every sponge's squeeze_bytes (mod.rs:256-270), cut from the canonical integers on the device."""
+        return self.parameters.context(self.device).sponge_squeeze_bytes_batch(self.state, self.mode_tag, self.mode_index, num_bytes)
+
+    def squeeze_bits(self, num_bits: int) -> np.ndarray:
+        """[n][num_bits] bool: every sponge's squeeze_bits (mod.rs:272-286)."""
+        return self.parameters.context(self.device).sponge_squeeze_bits_batch(self.state, self.mode_tag, self.mode_index, num_bits)
 
     # SpongeExt
     def into_state(self):
