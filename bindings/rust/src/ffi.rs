@@ -113,6 +113,23 @@ extern "C" {
     pub fn pmx_merkle_verify_paths_dev(ctx: *mut pmx_ctx, d_leaves: *const u64, d_indices: *const u64, d_paths: *const u64,
                                        depth: usize, k: usize, d_root: *const u64, d_ok: *mut u8, d_work: *mut u64,
                                        stream: *mut c_void) -> c_int;
+    // trees of any arity (2 <= arity <= rate): the 2-to-1 layouts generalised, paths [k][depth][arity - 1][4]
+    pub fn pmx_merkle_ary_shape(n_leaves: usize, arity: u32, depth: *mut usize, n_nodes: *mut usize) -> c_int;
+    pub fn pmx_merkle_ary(ctx: *mut pmx_ctx, leaves: *const u64, n_leaves: usize, arity: u32, nodes: *mut u64, root: *mut u64) -> c_int;
+    pub fn pmx_merkle_ary_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_leaves: usize, arity: u32, stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ary_forest(ctx: *mut pmx_ctx, leaves: *const u64, n_trees: usize, leaves_per_tree: usize, arity: u32,
+                                 nodes: *mut u64, roots: *mut u64) -> c_int;
+    pub fn pmx_merkle_ary_forest_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_trees: usize, leaves_per_tree: usize, arity: u32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ary_paths(nodes: *const u64, n_leaves: usize, arity: u32, indices: *const u64, k: usize,
+                                paths_out: *mut u64) -> c_int;
+    pub fn pmx_merkle_ary_paths_dev(ctx: *mut pmx_ctx, d_nodes: *const u64, n_leaves: usize, arity: u32, d_indices: *const u64,
+                                    k: usize, d_paths: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ary_verify_paths(ctx: *mut pmx_ctx, leaves: *const u64, indices: *const u64, paths: *const u64, depth: usize,
+                                       arity: u32, k: usize, root: *const u64, ok_out: *mut u8) -> c_int;
+    pub fn pmx_merkle_ary_verify_paths_dev(ctx: *mut pmx_ctx, d_leaves: *const u64, d_indices: *const u64, d_paths: *const u64,
+                                           depth: usize, arity: u32, k: usize, d_root: *const u64, d_ok: *mut u8, d_work: *mut u64,
+                                           stream: *mut c_void) -> c_int;
     // device memory for the *_dev entry points
     pub fn pmx_device_alloc(device: c_int, d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_device_free(device: c_int, d_ptr: *mut c_void) -> c_int;

@@ -144,7 +144,8 @@ int pmx_ctx_width(const pmx_ctx *ctx);
  * The launchers pick a kernel family by width, exponent, schedule, modulus and batch size.  This
  * reports the choice for one call, through the launchers' own conditions, so that a benchmark's instruction accounting
  * cannot drift from the kernels: op = one of PMX_OP_*, n = units of the call (states, rows, compressions of one tree
- * level, sponges), len = in_len / out_len of an absorb / squeeze call (ignored otherwise).  Host only; nothing is
+ * level, sponges), len = in_len / out_len of an absorb / squeeze call, the arity of a PMX_OP_COMPRESS level when it is 3 or more (the
+ * engine does not depend on it; ignored otherwise).  Host only; nothing is
  * launched.  The reference has no counterpart (one code path, src/poseidon/mod.rs:95-118). */
 #define PMX_OP_PERMUTE 0
 #define PMX_OP_HASH 1
@@ -307,6 +308,50 @@ int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t
                             size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out);
 int pmx_merkle_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
                                 size_t depth, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream);
+
+/* ---- Merkle trees of any arity ---------------------------------------------------------------------
+ * The width people choose so that ONE permutation compresses `rate` children (octal trees at t = 9, quaternary at t = 5):
+ *   parent = (new; absorb([c_0 .. c_{arity-1}]); squeeze_native(1))[0]
+ *          = permute(state[capacity + j] = c_j for j < arity, every other element 0)[capacity]          for 2 <= arity <= rate,
+ * because absorbing at most `rate` elements into a fresh sponge permutes exactly once, at the squeeze (src/poseidon/mod.rs:126-135,
+ * 219-230, 324-328).  A tree of N leaves costs (N - 1) / (arity - 1) permutations and log_arity(N) levels.  arity 2 is the 2-to-1
+ * compression above: at arity 2 every array here is byte for byte what the pmx_merkle_2to1* / pmx_merkle_paths /
+ * pmx_merkle_verify_paths* entries produce and accept, and the same kernels run.  (No counterpart in the reference.)
+ * Shapes: n_leaves = arity^depth with depth >= 0 (one leaf is its own root, nothing is launched); pmx_merkle_ary_shape (host only)
+ *   gives depth and n_nodes = (arity^(depth+1) - 1) / (arity - 1), and refuses what every entry below refuses: arity < 2, a leaf count
+ *   that is no power of the arity, a node array whose byte size overflows size_t (PMX_ERR_ARG).
+ * nodes: [n_nodes][4], the leaves, then every level, root last; the _dev variants take d_nodes with the leaves in its first rows
+ *   and only enqueue.  nodes / root / roots may be NULL in the host entries.
+ * Forest, level-major like pmx_merkle_2to1_forest: level l of every tree, tree after tree.  With m = leaves_per_tree, tree b's node j
+ *   of level l is row  n_trees * (m + m/arity + ... + m/arity^(l-1)) + b * (m / arity^l) + j;  the last n_trees rows are the roots.
+ * Paths: [k][depth][arity - 1][4], bottom-up; per level the siblings in child order with the running node's own slot left out (the
+ *   running node is child (index / arity^level) % arity of its parent).
+ *   pmx_merkle_ary_paths: host-only gather over a node array; an index >= n_leaves is PMX_ERR_ARG and nothing is written.
+ *   pmx_merkle_ary_paths_dev: the same gather on the device, enqueue only - node array, indices and paths stay there.  Device-resident
+ *     indices are not validated: an index >= n_leaves gets an all-zero path (and fails verification by its range).
+ * Verification: ok[i] = 1 iff hashing leaves[i] up its path gives `root` and indices[i] < arity^depth.  One compression launch of all
+ *   k running nodes per level; d_work is [k][(arity + 1) * 4] u64 of scratch.
+ * Errors, nothing launched or written on any: PMX_ERR_ARG for arity < 2, a leaf count that is no power of the arity, byte sizes that
+ *   overflow, arity^depth beyond 64 bits, null pointers, an element array (d_nodes, d_leaves, d_paths, d_root, d_work) that is not
+ *   16-byte aligned (d_indices needs 8 bytes, d_ok any address); PMX_ERR_CONFIG for arity > rate: more children than the rate is a
+ *   hash row (pmx_hash_batch_dev with in_len = arity, out_len = 1), not a single compression.
+ * Engine: pmx_ctx_engine_info(ctx, PMX_OP_COMPRESS, n, len) names the engine of a level of n parents; len is the arity and does not
+ *   enter the choice (len 0 .. 2: the 2-to-1 launch, which alone can run on the quad engine - it needs rate 2). */
+int pmx_merkle_ary_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes);
+int pmx_merkle_ary(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root);
+int pmx_merkle_ary_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream);
+int pmx_merkle_ary_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint32_t arity,
+                          uint64_t *nodes, uint64_t *roots);
+int pmx_merkle_ary_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t leaves_per_tree, uint32_t arity, void *stream);
+int pmx_merkle_ary_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
+                         uint64_t *paths_out);
+int pmx_merkle_ary_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                             size_t k, uint64_t *d_paths, void *stream);
+int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                uint32_t arity, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out);
+int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                    size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
+                                    void *stream);
 
 /* ---- device groups: the batch sharded over the GPUs of one node -------------------------------------
  * The reference is single-threaded and has no distributed code; nothing in src/poseidon/mod.rs:62-183 couples one

@@ -1009,31 +1009,41 @@ extern "C" int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uin
 }
 
 // ---- Merkle 2-to-1 -------------------------------------------------------------------------------
+// one permutation compresses at most `rate` children (absorbing more into a fresh sponge permutes in between: a hash row)
+static int arity_fits(const pmx_ctx *ctx, uint32_t arity) {
+    if (arity == 2 && ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
+    if (arity > ctx->dev.rounds.rate)
+        return set_error(PMX_ERR_CONFIG, "arity %u exceeds the rate %u: more children than the rate is a hash row (pmx_hash_batch_dev), not a single compression",
+                         arity, ctx->dev.rounds.rate);
+    return PMX_OK;
+}
 // Level by level on the caller's stream: level l reads the n_leaves >> (l-1) nodes of level l-1 and writes
 // n_leaves >> l parents.  (Cutting the tree into subtrees on concurrent streams was measured SLOWER - 7.0 ms ->
 // 12.5 ms at 8 streams for 2^21 leaves - because the narrow levels are latency-bound, not launch-bound.)
-// A single tree is the forest below with n_trees = 1: this is the level loop of both, behind each entry's own shape checks.
-static int merkle_levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t total_leaves, void *stream) {
-    if (ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
+// A single tree is the forest below with n_trees = 1: this is the level loop of both, behind each entry's own shape checks - and of the
+// trees of any arity further down (pmx_merkle_ary*: level l is n_leaves / arity^l parents; arity 2 launches the 2-to-1 kernel).
+static int merkle_levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t total_leaves, uint32_t arity, void *stream) {
+    if (int rc = arity_fits(ctx, arity)) return rc;
     if (!aligned16(d_nodes)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
     PMX_BIND(ctx);
     size_t src = 0, width = total_leaves;
-    while (width > n_trees) {      // level l of all trees: [src, src + width) -> [src + width, src + width + width / 2)
-        PMX_HIP(launch_compress(ctx->dev, ctx->t, d_nodes + src * 4, d_nodes + (src + width) * 4, width / 2, (hipStream_t)stream));
+    while (width > n_trees) {      // level l of all trees: [src, src + width) -> [src + width, src + width + width / arity)
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_nodes + src * 4, d_nodes + (src + width) * 4, arity, width / arity, (hipStream_t)stream));
         src += width;
-        width /= 2;
+        width /= arity;
     }
     return PMX_OK;
 }
 // Host buffers (the caller has bound the device): upload the leaves, the levels, download all nodes and / or the last n_trees (the roots).
-static int merkle_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t total_leaves, size_t n_nodes, uint64_t *nodes, uint64_t *roots) {
+static int merkle_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t total_leaves, size_t n_nodes, uint32_t arity, uint64_t *nodes,
+                       uint64_t *roots) {
     int rc = PMX_OK;
     std::lock_guard<std::mutex> lock(ctx->host_lock);
     void *d = nullptr;
     if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
     StreamDrain drain{ctx};
     PMX_HIP(hipMemcpyAsync(d, leaves, total_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = merkle_levels_dev(ctx, (uint64_t *)d, n_trees, total_leaves, ctx->stream))) return rc;
+    if ((rc = merkle_levels_dev(ctx, (uint64_t *)d, n_trees, total_leaves, arity, ctx->stream))) return rc;
     if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
     if (roots) PMX_HIP(hipMemcpyAsync(roots, (uint64_t *)d + (n_nodes - n_trees) * 4, n_trees * 32, hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));
@@ -1043,7 +1053,7 @@ static int merkle_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, siz
 extern "C" int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream) {
     if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_dev: null pointer");
     if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
-    return merkle_levels_dev(ctx, d_nodes, 1, n_leaves, stream);
+    return merkle_levels_dev(ctx, d_nodes, 1, n_leaves, 2, stream);
 }
 
 extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint64_t *nodes, uint64_t *root) {
@@ -1052,7 +1062,7 @@ extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_le
     if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
     PMX_BIND(ctx);
     if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-    return merkle_host(ctx, leaves, 1, n_leaves, 2 * n_leaves - 1, nodes, root);
+    return merkle_host(ctx, leaves, 1, n_leaves, 2 * n_leaves - 1, 2, nodes, root);
     PMX_ABI_END
 }
 
@@ -1075,7 +1085,7 @@ extern "C" int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_
     if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest_dev: null pointer");
     size_t total = 0, n_nodes = 0;
     if (int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes)) return rc;
-    return merkle_levels_dev(ctx, d_nodes, n_trees, total, stream);
+    return merkle_levels_dev(ctx, d_nodes, n_trees, total, 2, stream);
 }
 
 extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint64_t *nodes,
@@ -1085,7 +1095,7 @@ extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size
     size_t total = 0, n_nodes = 0;
     if (int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes)) return rc;
     PMX_BIND(ctx);
-    return merkle_host(ctx, leaves, n_trees, total, n_nodes, nodes, roots);
+    return merkle_host(ctx, leaves, n_trees, total, n_nodes, 2, nodes, roots);
     PMX_ABI_END
 }
 
@@ -1130,7 +1140,7 @@ extern "C" int pmx_merkle_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leave
         PMX_HIP(launch_path_pairs(cur, d_paths, d_indices, depth, level, pairs, k, st));
         PMX_HIP(launch_compress(ctx->dev, ctx->t, pairs, cur, k, st));
     }
-    PMX_HIP(launch_path_check(cur, d_root, d_indices, depth, d_ok, k, st));
+    PMX_HIP(launch_path_check(cur, d_root, d_indices, (uint64_t)1 << depth, d_ok, k, st));   // depth < 64 (checked above)
     return PMX_OK;
 }
 
@@ -1160,6 +1170,194 @@ extern "C" int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, con
     PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
     PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = pmx_merkle_verify_paths_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, k, d_root, (uint8_t *)d3, d_work, ctx->stream))) return rc;
+    PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// ---- trees of any arity ------------------------------------------------------------------------------------------------
+// The 2-to-1 layouts generalised (at arity 2 every array is byte for byte the one the entries above produce and accept): a parent is
+// (new; absorb(its arity children); squeeze_native(1))[0], one permutation for arity <= rate (mod.rs:126-135, 219-230, 324-328).  The
+// levels run through merkle_levels_dev / merkle_host above; only the shapes and the paths are new here.
+// depth = log_arity(n_leaves), n_nodes = n_leaves + n_leaves / arity + ... + 1; refused when n_nodes * 32 does not fit size_t.
+static int ary_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
+    if (arity < 2) return set_error(PMX_ERR_ARG, "arity must be at least 2");
+    if (n_leaves == 0) return set_error(PMX_ERR_ARG, "n_leaves must be a power of the arity");
+    size_t d = 0, nodes = 0;
+    for (size_t width = n_leaves;; width /= arity, ++d) {
+        if (width > SIZE_MAX / 32 - nodes) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
+        nodes += width;
+        if (width == 1) break;
+        if (width % arity) return set_error(PMX_ERR_ARG, "n_leaves must be a power of the arity");
+    }
+    *depth = d;
+    *n_nodes = nodes;
+    return PMX_OK;
+}
+// arity^depth, the number of leaves of a tree given by its depth; refused when it does not fit 64 bits
+static int ary_leaves(uint32_t arity, size_t depth, uint64_t *out) {
+    if (arity < 2) return set_error(PMX_ERR_ARG, "arity must be at least 2");
+    uint64_t n = 1;
+    for (size_t l = 0; l < depth; ++l) {
+        if (n > UINT64_MAX / arity) return set_error(PMX_ERR_ARG, "arity^depth overflows 64 bits");
+        n *= arity;
+    }
+    *out = n;
+    return PMX_OK;
+}
+static int ary_forest_shape(size_t n_trees, size_t leaves_per_tree, uint32_t arity, size_t *total_leaves, size_t *total_nodes) {
+    size_t depth = 0, tree_nodes = 0;
+    if (int rc = ary_shape(leaves_per_tree, arity, &depth, &tree_nodes)) return rc;
+    if (n_trees == 0) return set_error(PMX_ERR_ARG, "a forest needs n_trees >= 1");
+    if (n_trees > (SIZE_MAX / 32) / tree_nodes) return set_error(PMX_ERR_ARG, "forest byte size overflows size_t");
+    *total_leaves = n_trees * leaves_per_tree;
+    *total_nodes = n_trees * tree_nodes;
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_ary_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
+    if (!depth || !n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_shape: null pointer");
+    return ary_shape(n_leaves, arity, depth, n_nodes);
+}
+
+extern "C" int pmx_merkle_ary_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_dev: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    return merkle_levels_dev(ctx, d_nodes, 1, n_leaves, arity, stream);
+}
+
+extern "C" int pmx_merkle_ary(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_ary")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ary: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    return merkle_host(ctx, leaves, 1, n_leaves, n_nodes, arity, nodes, root);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_ary_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t leaves_per_tree, uint32_t arity, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_forest_dev: null pointer");
+    size_t total = 0, n_nodes = 0;
+    if (int rc = ary_forest_shape(n_trees, leaves_per_tree, arity, &total, &n_nodes)) return rc;
+    return merkle_levels_dev(ctx, d_nodes, n_trees, total, arity, stream);
+}
+
+extern "C" int pmx_merkle_ary_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint32_t arity,
+                                     uint64_t *nodes, uint64_t *roots) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_forest")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_forest: null pointer");
+    size_t total = 0, n_nodes = 0;
+    if (int rc = ary_forest_shape(n_trees, leaves_per_tree, arity, &total, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    return merkle_host(ctx, leaves, n_trees, total, n_nodes, arity, nodes, roots);
+    PMX_ABI_END
+}
+
+// ---- openings: per level the arity - 1 siblings in child order, the running node's own slot left out -----------------------------
+extern "C" int pmx_merkle_ary_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
+                                    uint64_t *paths_out) {
+    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_paths: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    for (size_t i = 0; i < k; ++i)     // (before anything is written)
+        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
+    const size_t sib = arity - 1;
+    for (size_t i = 0; i < k; ++i) {
+        size_t idx = (size_t)indices[i], first = 0, width = n_leaves;   // first node of the current level, its width
+        for (size_t level = 0; level < depth; ++level) {
+            const size_t digit = idx % arity, base = first + (idx - digit);
+            uint64_t *row = paths_out + (i * depth + level) * sib * 4;
+            std::memcpy(row, nodes + base * 4, digit * 32);
+            std::memcpy(row + digit * 4, nodes + (base + digit + 1) * 4, (sib - digit) * 32);
+            first += width;
+            width /= arity;
+            idx /= arity;
+        }
+    }
+    return PMX_OK;
+}
+
+// the same gather on the device: nodes, indices and paths stay where they are (an index >= n_leaves, which the host cannot see, gets
+// an all-zero path)
+extern "C" int pmx_merkle_ary_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                        size_t k, uint64_t *d_paths, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_paths_dev: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0 || depth == 0) return PMX_OK;
+    const size_t per = depth * (arity - 1);     // elements per path (depth <= 64, arity <= PMX_MAX_WIDTH)
+    if (k > (SIZE_MAX / 32) / per || k > ((size_t)0x7fffffff * 64) / per) return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_nodes) || !aligned16(d_paths)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    PMX_BIND(ctx);
+    PMX_HIP(launch_paths_gather(d_nodes, n_leaves, arity, depth, d_indices, d_paths, k, (hipStream_t)stream));
+    return PMX_OK;
+}
+
+// pmx_merkle_verify_paths_dev for any arity: per level a gather kernel lays the arity children of every path's parent out as the rows
+// one tree level has, and the compression launcher of that arity writes the parents back into cur.
+// d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).
+extern "C" int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                               size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
+                                               void *stream) {
+    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths_dev: null pointer");
+    uint64_t n_leaves = 0;
+    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    // (depth <= 64 and arity <= PMX_MAX_WIDTH here: the products below stay small)
+    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
+        return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_leaves) || !aligned16(d_paths) || !aligned16(d_work) || !aligned16(d_root)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    PMX_BIND(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *cur = d_work, *rows = d_work + k * 4;
+    PMX_HIP(hipMemcpyAsync(cur, d_leaves, k * 32, hipMemcpyDeviceToDevice, st));
+    uint64_t pow = 1;     // arity^level
+    for (size_t level = 0; level < depth; ++level, pow *= arity) {
+        PMX_HIP(launch_path_children(cur, d_paths, d_indices, depth, level, pow, arity, rows, k, st));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
+    }
+    PMX_HIP(launch_path_check(cur, d_root, d_indices, n_leaves, d_ok, k, st));
+    return PMX_OK;
+}
+
+// Host buffers: one upload of (leaves, indices, paths, root), `depth` level steps on the device, one download of ok.
+extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                           uint32_t arity, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_verify_paths")
+    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths: null pointer");
+    uint64_t n_leaves = 0;
+    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    if (k > (SIZE_MAX / 64) / (arity + 2) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
+        return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    PMX_BIND(ctx);
+    int rc = PMX_OK;
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    // slot 0: leaves [k][4] | work [k][(arity + 1) * 4];  slot 1: paths [k][depth][arity - 1][4];  slot 2: root [4] | indices [k];  slot 3: ok [k]
+    const size_t path_bytes = k * depth * (arity - 1) * 32;
+    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, k * (arity + 2) * 32, &d0))) return rc;
+    if ((rc = ctx_scratch(ctx, 1, path_bytes, &d1))) return rc;
+    if ((rc = ctx_scratch(ctx, 2, 32 + k * 8, &d2))) return rc;
+    if ((rc = ctx_scratch(ctx, 3, k, &d3))) return rc;
+    uint64_t *d_leaves = (uint64_t *)d0, *d_work = d_leaves + k * 4, *d_root = (uint64_t *)d2, *d_idx = d_root + 4;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d_leaves, leaves, k * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (path_bytes) PMX_HIP(hipMemcpyAsync(d1, paths, path_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = pmx_merkle_ary_verify_paths_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, k, d_root, (uint8_t *)d3, d_work, ctx->stream)))
+        return rc;
     PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;

@@ -754,6 +754,32 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
 }
 
+// arity-to-1 compression, the primitive of the wide trees (2 <= arity <= rate, a run-time value):
+//   out = (new; absorb([c_0 .. c_{arity-1}]); squeeze_native(1))[0]
+//       = permute(state with state[capacity + j] = c_j for j < arity, rest 0)[capacity]
+// for the same reason as above (mod.rs:126-135, 219-230, 324-328).  One permutation site, 32 arity contiguous bytes in and 32 out
+// per unit; the rate lanes from `arity` on stay the zeros of e.zero().  The child loop stays rolled: its body selects the state
+// element at run time, and unrolled rate times it is more code than it is worth in front of the permutation.
+template <class Engine>
+__global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
+    compress_ary_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ in, uint32_t arity,
+                        uint64_t *__restrict__ out, size_t n) {
+    Engine e(d, consts);
+    const size_t gid = Engine::unit();
+    const bool active = gid < n;
+    const uint32_t *row = reinterpret_cast<const uint32_t *>(in + (active ? gid : 0) * (size_t)arity * 4);
+    e.zero();
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 0; j < arity; ++j) {
+        const uint32_t at = e.c.capacity + j;
+        // each child is loaded by the lane that holds its state element only
+        if (e.owns(at)) e.set(at, e.from_abi(abi_load(row + 8 * j)));
+    }
+    e.permute(e.c.capacity, e.c.capacity + 1, e.c.capacity >= 1);   // only the digest lane of the result is read; lane 0 (capacity) went in as zero
+    const Abi digest = e.to_abi(e.get(e.c.capacity));
+    if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
+}
+
 // (per-lane engines: every lane keeps its own cursor and length - lanes of a wave may absorb rows of different lengths; a lane whose
 // row is empty absorbs nothing and leaves its mode words alone, mod.rs:234-236)
 template <class Engine, class Rows>
@@ -997,6 +1023,12 @@ struct Launch {
                            c.consts, in, out, n);
         return hipGetLastError();
     }
+    static hipError_t compress_ary(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st) {
+        allow_lds(compress_ary_kernel<Engine>, Engine::lds_bytes(c, t));
+        hipLaunchKernelGGL(compress_ary_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                           c.consts, in, arity, out, n);
+        return hipGetLastError();
+    }
     // absorb / squeeze: per-lane kernels, or - on an engine whose permutation must stay wave-uniform - passes on its permutation
     // (pmx_sponge_plan.hpp).  Only the form the engine has is instantiated.
     template <class Rows>
@@ -1091,7 +1123,8 @@ struct Launch {
 template <class Engine>
 static const EngineOps &engine_ops() {
     using L = Launch<Engine>;
-    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::absorb, &L::absorb_varlen, &L::squeeze, &Engine::lds_bytes, &L::describe};
+    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::compress_ary, &L::absorb, &L::absorb_varlen, &L::squeeze,
+                                      &Engine::lds_bytes, &L::describe};
     return ops;
 }
 
@@ -1192,6 +1225,13 @@ hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
     return select_engine(c, t, PMX_OP_COMPRESS, n)->compress(c, t, in, out, n, st);
 }
+// arity 2 IS the 2-to-1 launch (the quad engine included, which needs rate 2 and so never meets a wider row); a wider row goes to the
+// compress_ary kernel of the engine the same choice names.  (An arity beyond the rate would index past the state: refused here too.)
+hipError_t launch_compress_ary(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st) {
+    if (arity < 2 || arity > c.rounds.rate) return hipErrorInvalidValue;
+    if (arity == 2) return launch_compress(c, t, in, out, n, st);
+    return select_engine(c, t, PMX_OP_COMPRESS, n)->compress_ary(c, t, in, out, arity, n, st);
+}
 hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch) {
     return select_engine(c, t, PMX_OP_ABSORB, n)->absorb(c, t, states, tag, index, in, in_len, n, st, scratch);
@@ -1246,14 +1286,54 @@ __global__ void __launch_bounds__(256) path_pairs_kernel(const uint4 *__restrict
     pairs[gid] = from_cur ? cur[i * 2 + half] : paths[(i * depth + level) * 2 + half];
 }
 
+// the same for a tree of any arity (pmx_merkle_ary_verify_paths_dev): 2 arity lanes per path, one 16-byte quarter of a child each.
+// Row i of `rows` is the arity children of path i's parent at `level`: the running node at digit (index / arity^level) % arity, the
+// arity - 1 siblings of paths[i][level] in child order around it.  pow = arity^level (the caller's; >= 1).  The digit is below the
+// arity whatever the index holds, so an index that names no leaf still reads inside the arrays.
+__global__ void __launch_bounds__(256) path_children_kernel(const uint4 *__restrict__ cur, const uint4 *__restrict__ paths,
+                                                            const uint64_t *__restrict__ indices, size_t depth, size_t level, uint64_t pow,
+                                                            uint32_t arity, uint4 *__restrict__ rows, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per = 2 * (size_t)arity, i = gid / per;
+    if (i >= k) return;
+    const uint32_t quarter = (uint32_t)(gid - i * per), child = quarter >> 1, half = quarter & 1;
+    const uint32_t digit = (uint32_t)((indices[i] / pow) % arity);
+    const uint32_t sibling = child < digit ? child : child - 1;   // the running node's own slot is left out of the path
+    rows[gid] = child == digit ? cur[i * 2 + half] : paths[((i * depth + level) * (arity - 1) + sibling) * 2 + half];
+}
+
+// The opening itself on the device (pmx_merkle_ary_paths_dev): from the node array (leaves, then every level, root last) to paths
+// [k][depth][arity - 1][4], one 16-byte quarter per lane.  Device-resident indices are not validated by the host: an index that names
+// no leaf gets an all-zero path, and nothing outside the node array is read.
+__global__ void __launch_bounds__(256) paths_gather_kernel(const uint4 *__restrict__ nodes, uint64_t n_leaves, uint32_t arity, size_t depth,
+                                                           const uint64_t *__restrict__ indices, uint4 *__restrict__ paths, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per_level = 2 * (size_t)(arity - 1), per = depth * per_level, i = gid / per;
+    if (i >= k) return;
+    const size_t rest = gid - i * per, level = rest / per_level;
+    const uint32_t quarter = (uint32_t)(rest - level * per_level), sibling = quarter >> 1, half = quarter & 1;
+    uint64_t idx = indices[i], first = 0, width = n_leaves;   // the running node's index in its level, the level's first node, its width
+    if (idx >= n_leaves) {
+        paths[gid] = make_uint4(0, 0, 0, 0);
+        return;
+    }
+    for (size_t l = 0; l < level; ++l) {
+        first += width;
+        width /= arity;
+        idx /= arity;
+    }
+    const uint32_t digit = (uint32_t)(idx % arity);
+    const uint32_t child = sibling < digit ? sibling : sibling + 1;
+    paths[gid] = nodes[(first + (idx - digit) + child) * 2 + half];
+}
+
+// ok[i] = the running node equals the root and indices[i] < limit, the number of leaves a tree of this depth has (2^depth, arity^depth)
 __global__ void __launch_bounds__(256) path_check_kernel(const uint4 *__restrict__ cur, const uint4 *__restrict__ root,
-                                                         const uint64_t *__restrict__ indices, size_t depth,
+                                                         const uint64_t *__restrict__ indices, uint64_t limit,
                                                          uint8_t *__restrict__ ok, size_t k) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= k) return;
     const uint4 a = cur[i * 2], b = cur[i * 2 + 1], ra = root[0], rb = root[1];
     const bool same = a.x == ra.x && a.y == ra.y && a.z == ra.z && a.w == ra.w && b.x == rb.x && b.y == rb.y && b.z == rb.z && b.w == rb.w;
-    ok[i] = (same && (indices[i] >> depth) == 0) ? 1 : 0;   // depth < 64 (checked by the caller)
+    ok[i] = (same && indices[i] < limit) ? 1 : 0;
 }
 
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,
@@ -1262,10 +1342,22 @@ hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const u
                        reinterpret_cast<const uint4 *>(paths), indices, depth, level, reinterpret_cast<uint4 *>(pairs), k);
     return hipGetLastError();
 }
-hipError_t launch_path_check(const uint64_t *cur, const uint64_t *root, const uint64_t *indices, size_t depth, uint8_t *ok,
+hipError_t launch_path_children(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level, uint64_t pow,
+                                uint32_t arity, uint64_t *rows, size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(path_children_kernel, dim3((unsigned)((k * 2 * arity + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),
+                       reinterpret_cast<const uint4 *>(paths), indices, depth, level, pow, arity, reinterpret_cast<uint4 *>(rows), k);
+    return hipGetLastError();
+}
+hipError_t launch_paths_gather(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices, uint64_t *paths,
+                               size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(paths_gather_kernel, dim3((unsigned)((k * depth * 2 * (arity - 1) + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const uint4 *>(nodes), (uint64_t)n_leaves, arity, depth, indices, reinterpret_cast<uint4 *>(paths), k);
+    return hipGetLastError();
+}
+hipError_t launch_path_check(const uint64_t *cur, const uint64_t *root, const uint64_t *indices, uint64_t limit, uint8_t *ok,
                              size_t k, hipStream_t st) {
     hipLaunchKernelGGL(path_check_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),
-                       reinterpret_cast<const uint4 *>(root), indices, depth, ok, k);
+                       reinterpret_cast<const uint4 *>(root), indices, limit, ok, k);
     return hipGetLastError();
 }
 #endif  // PMX_TU

@@ -16,6 +16,8 @@ hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_
                        size_t n, hipStream_t st);
 // out[i] = 2-to-1 compression of in[2i], in[2i+1]   (rate >= 2)
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
+// out[i] = arity-to-1 compression of in[arity i .. arity i + arity)   (2 <= arity <= rate; arity 2 is launch_compress)
+hipError_t launch_compress_ary(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st);
 // Device scratch for the pass lists of the drivers that run as passes (pmx_device.hip: sponge_passes): `get` hands out at least
 // `bytes` bytes that stay valid for everything enqueued on `st` by this call, `done` is called once behind the call's last launch
 // (pmx_api.cpp: a pool of blocks owned by the context, each released by an event recorded there).  Engines that need no lists
@@ -55,6 +57,7 @@ struct EngineOps {
     hipError_t (*hash)(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, size_t n,
                        hipStream_t st);
     hipError_t (*compress)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
+    hipError_t (*compress_ary)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st);
     hipError_t (*absorb)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
                          size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch);
     hipError_t (*absorb_varlen)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
@@ -67,10 +70,18 @@ struct EngineOps {
 };
 
 // Authentication paths, one level per step (pmx_merkle_verify_paths_dev): pairs[i] = (cur[i], sibling) or (sibling, cur[i])
-// by bit `level` of indices[i], sibling = paths[i][level]; then ok[i] = (cur[i] == root) && indices[i] < 2^depth.
+// by bit `level` of indices[i], sibling = paths[i][level]; then ok[i] = (cur[i] == root) && indices[i] < limit (2^depth).
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,
                              uint64_t *pairs, size_t k, hipStream_t st);
-hipError_t launch_path_check(const uint64_t *cur, const uint64_t *root, const uint64_t *indices, size_t depth, uint8_t *ok,
+hipError_t launch_path_check(const uint64_t *cur, const uint64_t *root, const uint64_t *indices, uint64_t limit, uint8_t *ok,
                              size_t k, hipStream_t st);
+// The same for any arity (pmx_merkle_ary_verify_paths_dev; paths [k][depth][arity - 1][4]): rows[i] = the arity children of path i's
+// parent at `level`, cur[i] at digit (indices[i] / pow) % arity with pow = arity^level; the check above with limit = arity^depth.
+hipError_t launch_path_children(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level, uint64_t pow,
+                                uint32_t arity, uint64_t *rows, size_t k, hipStream_t st);
+// The opening on the device (pmx_merkle_ary_paths_dev): paths[i] = the siblings of leaf indices[i] and of its ancestors out of `nodes`
+// (zeros for an index >= n_leaves).  depth >= 1, k >= 1.
+hipError_t launch_paths_gather(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices, uint64_t *paths,
+                               size_t k, hipStream_t st);
 
 }  // namespace pmx

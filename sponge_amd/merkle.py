@@ -1,10 +1,10 @@
-"""2-to-1 Poseidon Merkle trees on the GPU: the natural consumer of the compression mode (SURVEY section 8(f) rank 4;
+"""Poseidon Merkle trees on the GPU: the natural consumer of the compression mode (SURVEY section 8(f) rank 4;
 the container itself lives upstream in ark-crypto-primitives, not in arkworks-rs/sponge).
 
-A parent is  (PoseidonSponge::new; absorb([left, right]); squeeze_native_field_elements(1))[0]
-(reference src/poseidon/mod.rs:219-254, 321-341).  Nodes are kept as one array [2m-1][4]: leaves, then every level,
-root last - the layout pmx_merkle_2to1 produces.  Authentication paths are verified in batch: all paths advance
-one level per hash_batch call."""
+A parent is  (PoseidonSponge::new; absorb(its children); squeeze_native_field_elements(1))[0]
+(reference src/poseidon/mod.rs:219-254, 321-341): two children by default (pmx_merkle_2to1), `arity` of them - at most
+the rate, one permutation each - with arity > 2 (pmx_merkle_ary).  Nodes are kept as one array [n_nodes][4]: leaves,
+then every level, root last.  Authentication paths are verified in batch: all paths advance one level per launch."""
 from __future__ import annotations
 
 from typing import List
@@ -14,59 +14,106 @@ import numpy as np
 import ctypes
 
 from . import _lib
-from .poseidon import PoseidonConfig
+from .poseidon import PoseidonConfig, merkle_ary_shape
 
 
 class MerkleTree:
-    def __init__(self, parameters: PoseidonConfig, leaves: np.ndarray, device: int = 0):
+    def __init__(self, parameters: PoseidonConfig, leaves: np.ndarray, device: int = 0, arity: int = 2):
         leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
         m = leaves.shape[0]
-        assert m >= 1 and (m & (m - 1)) == 0, "number of leaves must be a power of two"
+        assert arity >= 2, "a parent has at least two children"
+        if arity == 2:
+            assert m >= 1 and (m & (m - 1)) == 0, "number of leaves must be a power of two"
+            self.depth = m.bit_length() - 1
+        else:
+            self.depth, _ = merkle_ary_shape(m, arity)     # PmxError: the number of leaves must be a power of the arity
         self.parameters = parameters
         self.device = device
+        self.arity = arity
         self.n_leaves = m
-        self.depth = m.bit_length() - 1
         if m == 1:
             self.nodes, self._root = leaves.copy(), leaves[0].copy()
-        else:
+        elif arity == 2:
             self.nodes, self._root = parameters.context(device).merkle_2to1(leaves)
+        else:
+            self.nodes, self._root = parameters.context(device).merkle_ary(leaves, arity)
 
     @property
     def root(self) -> np.ndarray:
         return self._root
 
     def level_offset(self, level: int) -> int:
-        """Index of the first node of `level` (0 = leaves) in `nodes`."""
-        return 2 * self.n_leaves - (self.n_leaves >> (level - 1) if level else 2 * self.n_leaves)
+        """Index of the first node of `level` (0 = leaves) in `nodes`: n + n / arity + ... + n / arity^(level - 1)."""
+        return sum(self.n_leaves // self.arity ** l for l in range(level))
 
     def path(self, leaf_index: int) -> np.ndarray:
-        """Sibling of the leaf, then of each ancestor, bottom-up: [depth][4]."""
+        """Siblings of the leaf, then of each ancestor, bottom-up: [depth][4] (arity 2), [depth][arity - 1][4] otherwise."""
         assert 0 <= leaf_index < self.n_leaves
         return self.paths([leaf_index])[0]
 
+    def _path_shape(self, k: int):
+        return (k, self.depth, 4) if self.arity == 2 else (k, self.depth, self.arity - 1, 4)
+
     def paths(self, leaf_indices) -> np.ndarray:
-        """[k][depth][4] for k leaves (pmx_merkle_paths: a host-side gather over the node array)."""
+        """[k][depth][4] for k leaves (pmx_merkle_paths: a host-side gather over the node array); with arity > 2
+        [k][depth][arity - 1][4], per level the siblings in child order without the running node (pmx_merkle_ary_paths)."""
         idx = np.ascontiguousarray(leaf_indices, dtype=np.uint64)
-        out = np.zeros((idx.shape[0], self.depth, 4), dtype=np.uint64)
+        out = np.zeros(self._path_shape(idx.shape[0]), dtype=np.uint64)
         nodes = np.ascontiguousarray(self.nodes, dtype=np.uint64)
-        _lib.check(_lib.lib().pmx_merkle_paths(ctypes.c_void_p(nodes.ctypes.data), self.n_leaves, ctypes.c_void_p(idx.ctypes.data),
-                                               idx.shape[0], ctypes.c_void_p(out.ctypes.data)))
+        if self.arity == 2:
+            _lib.check(_lib.lib().pmx_merkle_paths(ctypes.c_void_p(nodes.ctypes.data), self.n_leaves, ctypes.c_void_p(idx.ctypes.data),
+                                                   idx.shape[0], ctypes.c_void_p(out.ctypes.data)))
+        else:
+            _lib.check(_lib.lib().pmx_merkle_ary_paths(ctypes.c_void_p(nodes.ctypes.data), self.n_leaves, self.arity,
+                                                       ctypes.c_void_p(idx.ctypes.data), idx.shape[0], ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def paths_dev(self, leaf_indices) -> np.ndarray:
+        """paths() through the device-side gather (pmx_merkle_ary_paths_dev): node array and indices are uploaded, the paths
+        gathered there and downloaded.  (A caller whose node array already lives on the device calls
+        Context.merkle_ary_paths_dev on its own pointers; this is that call with the copies around it.)  Unlike paths(), an
+        index >= n_leaves is not an error here: its path comes back all zero."""
+        idx = np.ascontiguousarray(leaf_indices, dtype=np.uint64)
+        out = np.zeros(self._path_shape(idx.shape[0]), dtype=np.uint64)
+        if out.size == 0:
+            return out
+        nodes = np.ascontiguousarray(self.nodes, dtype=np.uint64)
+        L, ctx, dev = _lib.lib(), self.parameters.context(self.device), self.device
+        blocks: List[ctypes.c_void_p] = []
+        try:
+            for nbytes in (nodes.nbytes, idx.nbytes, out.nbytes):
+                d = ctypes.c_void_p()
+                _lib.check(L.pmx_device_alloc(dev, ctypes.byref(d), nbytes))
+                blocks.append(d)
+            d_nodes, d_idx, d_out = blocks
+            _lib.check(L.pmx_device_upload(dev, d_nodes, ctypes.c_void_p(nodes.ctypes.data), nodes.nbytes, None))
+            _lib.check(L.pmx_device_upload(dev, d_idx, ctypes.c_void_p(idx.ctypes.data), idx.nbytes, None))
+            ctx.merkle_ary_paths_dev(d_nodes, self.n_leaves, self.arity, d_idx, idx.shape[0], d_out, None)
+            _lib.check(L.pmx_device_download(dev, ctypes.c_void_p(out.ctypes.data), d_out, out.nbytes, None))
+            _lib.check(L.pmx_stream_synchronize(dev, None))
+        finally:
+            for d in blocks:
+                L.pmx_device_free(dev, d)
         return out
 
 
 def verify_paths(parameters: PoseidonConfig, leaves: np.ndarray, indices, paths: np.ndarray, root: np.ndarray,
-                 device: int = 0) -> np.ndarray:
+                 device: int = 0, arity: int = 2) -> np.ndarray:
     """k authentication paths at once: leaves [k][4], indices [k], paths [k][depth][4] -> bool[k]
     (pmx_merkle_verify_paths: one upload, one device step per level, one download; an index with bits at or above
-    `depth` names no leaf and verifies as False)."""
+    `depth` names no leaf and verifies as False).  With arity > 2 paths are [k][depth][arity - 1][4]
+    (pmx_merkle_ary_verify_paths; an index >= arity^depth verifies as False)."""
     cur = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
     idx = np.ascontiguousarray(indices, dtype=np.uint64)
     paths = np.ascontiguousarray(paths, dtype=np.uint64)
     k = cur.shape[0]
-    depth = paths.shape[1] if paths.ndim == 3 else 0
     root = np.ascontiguousarray(root, dtype=np.uint64).reshape(4)
-    ok = np.zeros(k, dtype=np.uint8)
     ctx = parameters.context(device)
+    if arity != 2:
+        depth = paths.shape[1] if paths.ndim == 4 else 0
+        return ctx.merkle_ary_verify_paths(cur, idx, paths, depth, arity, root).astype(bool)
+    depth = paths.shape[1] if paths.ndim == 3 else 0
+    ok = np.zeros(k, dtype=np.uint8)
     _lib.check(_lib.lib().pmx_merkle_verify_paths(ctx._h, ctypes.c_void_p(cur.ctypes.data), ctypes.c_void_p(idx.ctypes.data),
                                                   ctypes.c_void_p(paths.ctypes.data) if paths.size else None, depth, k,
                                                   ctypes.c_void_p(root.ctypes.data), ctypes.c_void_p(ok.ctypes.data)))

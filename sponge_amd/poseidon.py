@@ -169,6 +169,14 @@ def c_config(cfg: "PoseidonConfig") -> "_lib.PmxConfig":
     return c
 
 
+def merkle_ary_shape(n_leaves: int, arity: int) -> Tuple[int, int]:
+    """(depth, n_nodes) of the tree of `arity` over n_leaves = arity^depth leaves (pmx_merkle_ary_shape; host only).  PmxError for a
+    leaf count that is no power of the arity."""
+    depth, n_nodes = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.lib().pmx_merkle_ary_shape(n_leaves, arity, ctypes.byref(depth), ctypes.byref(n_nodes)))
+    return depth.value, n_nodes.value
+
+
 def varlen_rows(elems, offsets=None) -> Tuple[np.ndarray, np.ndarray]:
     """(elems [*][4], offsets [n+1]) of variable-length rows, contiguous u64: a list of [L_i][4] arrays (offsets None) is packed."""
     if offsets is None:
@@ -297,6 +305,51 @@ class Context:
 
     def merkle_2to1_forest_dev(self, d_nodes: int, n_trees: int, leaves_per_tree: int, stream: int = 0) -> None:
         _lib.check(_lib.lib().pmx_merkle_2to1_forest_dev(self._h, d_nodes, n_trees, leaves_per_tree, stream))
+
+    # ---- trees of any arity (2 <= arity <= rate; arity 2 is merkle_2to1) ---------------------------
+    def merkle_ary(self, leaves: np.ndarray, arity: int, want_nodes: bool = True):
+        """The tree over leaves [arity^depth][4] (pmx_merkle_ary): (nodes, root), nodes [n_nodes][4] - leaves, then every level, root
+        last - or None."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        depth, n_nodes = merkle_ary_shape(leaves.shape[0], arity)
+        nodes = np.zeros((n_nodes, 4), dtype=np.uint64) if want_nodes else None
+        root = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_merkle_ary(self._h, _ptr(leaves), leaves.shape[0], arity, _ptr(nodes), _ptr(root)))
+        return nodes, root
+
+    def merkle_ary_forest(self, leaves: np.ndarray, n_trees: int, arity: int, want_nodes: bool = True):
+        """n_trees trees over leaves [n_trees][m][4], advanced together level by level (pmx_merkle_ary_forest).  Returns (nodes, roots):
+        nodes level-major - all leaves, then level 1 of every tree, ... - or None."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        m = leaves.shape[0] // n_trees
+        assert m * n_trees == leaves.shape[0]
+        depth, tree_nodes = merkle_ary_shape(m, arity)
+        nodes = np.zeros((n_trees * tree_nodes, 4), dtype=np.uint64) if want_nodes else None
+        roots = np.zeros((n_trees, 4), dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_merkle_ary_forest(self._h, _ptr(leaves), n_trees, m, arity, _ptr(nodes), _ptr(roots)))
+        return nodes, roots
+
+    def merkle_ary_verify_paths(self, leaves, indices, paths, depth: int, arity: int, root) -> np.ndarray:
+        """k authentication paths [k][depth][arity - 1][4] at once (pmx_merkle_ary_verify_paths): uint8[k]."""
+        k = indices.shape[0]
+        ok = np.zeros(k, dtype=np.uint8)
+        _lib.check(_lib.lib().pmx_merkle_ary_verify_paths(self._h, _ptr(leaves), _ptr(indices), _ptr(paths) if paths.size else None, depth,
+                                                          arity, k, _ptr(root), _ptr(ok)))
+        return ok
+
+    def merkle_ary_dev(self, d_nodes: int, n_leaves: int, arity: int, stream: int = 0) -> None:
+        _lib.check(_lib.lib().pmx_merkle_ary_dev(self._h, d_nodes, n_leaves, arity, stream))
+
+    def merkle_ary_forest_dev(self, d_nodes: int, n_trees: int, leaves_per_tree: int, arity: int, stream: int = 0) -> None:
+        _lib.check(_lib.lib().pmx_merkle_ary_forest_dev(self._h, d_nodes, n_trees, leaves_per_tree, arity, stream))
+
+    def merkle_ary_paths_dev(self, d_nodes: int, n_leaves: int, arity: int, d_indices: int, k: int, d_paths: int, stream: int = 0) -> None:
+        """the opening on the device: d_paths [k][depth][arity - 1][4] from d_nodes (zeros for an index >= n_leaves)"""
+        _lib.check(_lib.lib().pmx_merkle_ary_paths_dev(self._h, d_nodes, n_leaves, arity, d_indices, k, d_paths, stream))
+
+    def merkle_ary_verify_paths_dev(self, d_leaves, d_indices, d_paths, depth: int, arity: int, k: int, d_root, d_ok, d_work, stream=0) -> None:
+        """d_work: [k][(arity + 1) * 4] u64 of scratch; d_ok: k bytes at any address."""
+        _lib.check(_lib.lib().pmx_merkle_ary_verify_paths_dev(self._h, d_leaves, d_indices, d_paths, depth, arity, k, d_root, d_ok, d_work, stream))
 
     # ---- device-pointer entry points (only enqueue; pointers are raw device addresses) ---------
     def permute_batch_dev(self, d_states: int, n: int, stream: int = 0) -> None:
