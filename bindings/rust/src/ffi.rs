@@ -130,6 +130,11 @@ extern "C" {
     pub fn pmx_merkle_ary_verify_paths_dev(ctx: *mut pmx_ctx, d_leaves: *const u64, d_indices: *const u64, d_paths: *const u64,
                                            depth: usize, arity: u32, k: usize, d_root: *const u64, d_ok: *mut u8, d_work: *mut u64,
                                            stream: *mut c_void) -> c_int;
+    // k leaves of a tree change, only their ancestors are recomputed; d_work: [k][(arity + 1) * 4] u64; root may be null
+    pub fn pmx_merkle_ary_update_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_leaves: usize, arity: u32, d_indices: *const u64,
+                                     d_new_leaves: *const u64, k: usize, d_work: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ary_update(ctx: *mut pmx_ctx, nodes: *mut u64, n_leaves: usize, arity: u32, indices: *const u64,
+                                 new_leaves: *const u64, k: usize, root: *mut u64) -> c_int;
     // device memory for the *_dev entry points
     pub fn pmx_device_alloc(device: c_int, d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_device_free(device: c_int, d_ptr: *mut c_void) -> c_int;

@@ -353,6 +353,38 @@ int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, cons
                                     size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
                                     void *stream);
 
+/* ---- leaf updates of a tree of any arity ------------------------------------------------------------
+ * k leaves of a tree change and only their ancestors are recomputed: at most k * depth permutations instead of the (N - 1) / (arity - 1)
+ * of a rebuild (the 8-ary tree over 2^21 leaves with k = 1024: at most 7 168 instead of 299 593).  The node array is the one
+ * pmx_merkle_ary[_dev] produces ([n_nodes][4]: leaves, then every level, root last; at arity 2 also the array of pmx_merkle_2to1*).
+ * Afterwards it is byte for byte what pmx_merkle_ary gives over the leaf row with new_leaves[i] at indices[i]; a node that is no
+ * ancestor of an updated leaf is not written at all (but see the whole levels of the device entry).
+ * pmx_merkle_ary_update_dev: everything device-resident, on the caller's stream.  It only enqueues and allocates nothing, so - unlike
+ *   the sponge drivers - it may be captured into a graph.  d_work is [k][(arity + 1) * 4] u64 of scratch, as for
+ *   pmx_merkle_ary_verify_paths_dev.  d_nodes, d_new_leaves and d_work are 16-byte aligned, d_indices 8-byte.  The new leaves are
+ *   scattered into the leaf rows; then, level by level, while k is below the number W of parents the level has: the arity children of
+ *   every update's parent are gathered, one compression launch of k rows runs, and the k digests are scattered to their parents (two
+ *   updates under one parent compute it twice and store identical bytes).  From the first level with k >= W on, that level and every
+ *   level above it run as the whole-level launches of pmx_merkle_ary_dev, which rewrite every node of those levels with the value it
+ *   has: an update never costs more permutations than a rebuild.
+ *   Device-resident indices are not validated.  An index >= n_leaves is ignored: its leaf and its ancestors are not written, and
+ *   nothing outside the arrays is read or written.  Indices must be distinct, or equal with equal leaves: two different leaves for one
+ *   index leave that leaf row unspecified (its two 16-byte halves may come from different updates); the tree above it is still the tree
+ *   of whatever landed.
+ *   n_leaves = 1: the leaf is the root, only the scatter runs.  k = 0: PMX_OK, nothing launched.
+ * pmx_merkle_ary_update: `nodes` is a host array and is not uploaded.  Every index is validated before anything is modified (an index
+ *   >= n_leaves is PMX_ERR_ARG naming it); duplicates are sequential updates, the last one wins.  The host packs the children rows of
+ *   the distinct ancestors of every level, one upload takes them to the device, each level is one compression launch and one scatter
+ *   of its digests into the next level's rows, one download brings all digests back; then leaves and digests are written into `nodes`
+ *   and the root into `root` (may be NULL).  Each distinct ancestor is permuted once.  A failure leaves `nodes` untouched.
+ * Errors, nothing launched or written on any: those of pmx_merkle_ary_paths_dev (PMX_ERR_ARG for arity < 2, a leaf count that is no power
+ *   of the arity, byte sizes that overflow, null pointers, misaligned device pointers, "batch too large" by the bounds of
+ *   pmx_merkle_ary_verify_paths_dev); PMX_ERR_CONFIG for arity > rate. */
+int pmx_merkle_ary_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                              const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream);
+int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices,
+                          const uint64_t *new_leaves, size_t k, uint64_t *root /* may be NULL */);
+
 /* ---- device groups: the batch sharded over the GPUs of one node -------------------------------------
  * The reference is single-threaded and has no distributed code; nothing in src/poseidon/mod.rs:62-183 couples one
  * sponge state to another, so n states are cut into `world` contiguous shards (pmx_shard_bounds), one per GPU, and

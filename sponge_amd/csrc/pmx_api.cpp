@@ -19,6 +19,7 @@
 #include "pmx_internal.hpp"
 #include "pmx_prepare.hpp"
 #include "pmx_launch.hpp"
+#include "pmx_merkle_plan.hpp"
 #include "pmx_sponge_plan.hpp"
 #include "pmx_squeeze_cut.hpp"
 
@@ -1360,6 +1361,87 @@ extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves,
         return rc;
     PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// ---- leaf updates of a tree of any arity ------------------------------------------------------------------------------------------
+// k leaves of a resident tree change: only their ancestors are recomputed, level by level.  While the k updates are fewer than the W
+// parents a level has, the level is  gather (the arity children of every update's parent, out of the node array) -> one compression launch
+// of k rows -> scatter (cur[i] to the parent's node); two updates under one parent compute it twice and store the same bytes.  From the
+// first level with k >= W on, the levels are the builder's own launches: an update never costs more permutations than a rebuild.
+// d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).  Enqueue only, nothing is allocated.
+extern "C" int pmx_merkle_ary_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                         const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_new_leaves || !d_work) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_update_dev: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (!aligned16(d_nodes) || !aligned16(d_new_leaves) || !aligned16(d_work)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
+    PMX_BIND(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *cur = d_work, *rows = d_work + k * 4;
+    PMX_HIP(launch_node_scatter(d_new_leaves, d_indices, 1, n_leaves, 0, d_nodes, k, st));
+    size_t first = 0, width = n_leaves;      // level l: its first node, its width
+    uint64_t pow = arity;                    // arity^(l+1)
+    for (size_t l = 0; l < depth; ++l, pow *= arity) {
+        const size_t parents = width / arity;
+        if (k >= parents) {     // the rest of the tree as whole levels
+            for (; width > 1; first += width, width /= arity)
+                PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_nodes + first * 4, d_nodes + (first + width) * 4, arity, width / arity, st));
+            break;
+        }
+        PMX_HIP(launch_node_children(d_nodes, d_indices, pow, n_leaves, first, arity, rows, k, st));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
+        PMX_HIP(launch_node_scatter(cur, d_indices, pow, n_leaves, first + width, d_nodes, k, st));
+        first += width;
+        width = parents;
+    }
+    return PMX_OK;
+}
+
+// Host buffers.  The node array stays on the host: the plan (pmx_merkle_plan.hpp) packs the children rows of every distinct ancestor, one
+// upload takes them to the device with the slots their digests go to, each level is one compression launch and one scatter, one download
+// brings all digests back, and only then is `nodes` written.
+extern "C" int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices,
+                                     const uint64_t *new_leaves, size_t k, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_update")
+    if (!ctx || !nodes || ((!indices || !new_leaves) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_update: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    const size_t bad = merkle_update_first_bad(indices, k, n_leaves);     // (before anything is written)
+    if (bad < k) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[bad]);
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    MerkleUpdatePlan plan;
+    merkle_update_plan(nodes, n_leaves, arity, indices, new_leaves, k, &plan);
+    const size_t n_rows = plan.n_rows();
+    std::vector<uint64_t> digests(n_rows * 4);
+    if (n_rows) {
+        PMX_BIND(ctx);
+        int rc = PMX_OK;
+        std::lock_guard<std::mutex> lock(ctx->host_lock);
+        // slot 0: rows [n_rows][arity][4] | slots [n_rows];  slot 1: digests [n_rows][4]
+        void *d0 = nullptr, *d1 = nullptr;
+        if ((rc = ctx_scratch(ctx, 0, plan.upload.size() * 8, &d0))) return rc;
+        if ((rc = ctx_scratch(ctx, 1, n_rows * 32, &d1))) return rc;
+        uint64_t *d_rows = (uint64_t *)d0, *d_slots = d_rows + n_rows * arity * 4, *d_dig = (uint64_t *)d1;
+        StreamDrain drain{ctx};
+        PMX_HIP(hipMemcpyAsync(d0, plan.upload.data(), plan.upload.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        for (size_t l = 1; l <= depth; ++l) {
+            const size_t r = plan.row_first[l], count = plan.level_rows(l);
+            PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_rows + r * arity * 4, d_dig + r * 4, arity, count, ctx->stream));
+            if (l < depth)
+                PMX_HIP(launch_node_scatter(d_dig + r * 4, d_slots + r, 1, plan.level_rows(l + 1) * arity, plan.row_first[l + 1] * arity, d_rows,
+                                            count, ctx->stream));
+        }
+        PMX_HIP(hipMemcpyAsync(digests.data(), d1, n_rows * 32, hipMemcpyDeviceToHost, ctx->stream));
+        PMX_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    merkle_update_apply(plan, new_leaves, digests.data(), nodes);
+    if (root) std::memcpy(root, nodes + (n_nodes - 1) * 4, 32);
     return PMX_OK;
     PMX_ABI_END
 }

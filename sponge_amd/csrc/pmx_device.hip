@@ -1336,6 +1336,46 @@ __global__ void __launch_bounds__(256) path_check_kernel(const uint4 *__restrict
     ok[i] = (same && indices[i] < limit) ? 1 : 0;
 }
 
+// ---- leaf updates of a resident tree (pmx_merkle_ary_update_dev, pmx_merkle_ary_update) -------------------------------------------
+// Pure data movement around launch_compress_ary, like the path kernels above.  The scatter: two lanes per element, one 16-byte half each,
+// dst[base + indices[i] / pow] = src[i] if indices[i] < limit.  The leaves go in with pow = 1, base = 0; the parents of level l + 1 with
+// pow = arity^(l+1), base = the level's first node (limit = n_leaves both times: index / pow is then below the level's width); the host
+// entry's digests go to explicit slots of its packed rows (pow = 1, limit = the slots the level has).  An index at or above the limit
+// stores nothing.  Two lanes that store to one element store what their sources hold: equal sources, equal bytes.  pow >= 1.
+__global__ void __launch_bounds__(256) node_scatter_kernel(const uint4 *__restrict__ src, const uint64_t *__restrict__ indices, uint64_t pow,
+                                                           uint64_t limit, uint64_t base, uint4 *__restrict__ dst, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, i = gid >> 1;
+    if (i >= k) return;
+    const uint64_t idx = indices[i];
+    if (idx >= limit) return;
+    dst[(base + idx / pow) * 2 + (gid & 1)] = src[gid];
+}
+
+// The gather: 2 arity lanes per update, one 16-byte half of a child each.  Row i of `rows` is the arity children of update i's parent
+// p = indices[i] / pow (pow = arity^(l+1)) out of level l, whose first node is `first`: nodes[first + p * arity ...].  An index that names no
+// leaf (>= n_leaves) gathers the row of parent 0 - in range like every other, and its parent is never stored (the scatter above).
+__global__ void __launch_bounds__(256) node_children_kernel(const uint4 *__restrict__ nodes, const uint64_t *__restrict__ indices, uint64_t pow,
+                                                            uint64_t n_leaves, uint64_t first, uint32_t arity, uint4 *__restrict__ rows,
+                                                            size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per = 2 * (size_t)arity, i = gid / per;
+    if (i >= k) return;
+    const uint64_t idx = indices[i], p = idx < n_leaves ? idx / pow : 0;
+    rows[gid] = nodes[(first + p * arity) * 2 + (gid - i * per)];
+}
+
+hipError_t launch_node_scatter(const uint64_t *src, const uint64_t *indices, uint64_t pow, uint64_t limit, uint64_t base, uint64_t *dst,
+                               size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)((k * 2 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(src),
+                       indices, pow, limit, base, reinterpret_cast<uint4 *>(dst), k);
+    return hipGetLastError();
+}
+hipError_t launch_node_children(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first, uint32_t arity,
+                                uint64_t *rows, size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(node_children_kernel, dim3((unsigned)((k * 2 * arity + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const uint4 *>(nodes), indices, pow, n_leaves, first, arity, reinterpret_cast<uint4 *>(rows), k);
+    return hipGetLastError();
+}
+
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,
                              uint64_t *pairs, size_t k, hipStream_t st) {
     hipLaunchKernelGGL(path_pairs_kernel, dim3((unsigned)((k * 4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),

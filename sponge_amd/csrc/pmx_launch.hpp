@@ -83,5 +83,11 @@ hipError_t launch_path_children(const uint64_t *cur, const uint64_t *paths, cons
 // (zeros for an index >= n_leaves).  depth >= 1, k >= 1.
 hipError_t launch_paths_gather(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices, uint64_t *paths,
                                size_t k, hipStream_t st);
+// Leaf updates (pmx_merkle_ary_update*): dst[base + indices[i] / pow] = src[i] for indices[i] < limit (elements of 4 words; pow >= 1), and
+// rows[i] = the arity children nodes[first + p * arity ...] of parent p = indices[i] / pow (p = 0 for an index >= n_leaves).  k >= 1.
+hipError_t launch_node_scatter(const uint64_t *src, const uint64_t *indices, uint64_t pow, uint64_t limit, uint64_t base, uint64_t *dst,
+                               size_t k, hipStream_t st);
+hipError_t launch_node_children(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first, uint32_t arity,
+                                uint64_t *rows, size_t k, hipStream_t st);
 
 }  // namespace pmx

@@ -68,6 +68,15 @@ class MerkleTree:
                                                        ctypes.c_void_p(idx.ctypes.data), idx.shape[0], ctypes.c_void_p(out.ctypes.data)))
         return out
 
+    def update(self, leaf_indices, leaves) -> None:
+        """Replace leaves leaf_indices[i] by leaves[i] and recompute only their ancestors (pmx_merkle_ary_update, any arity): `nodes`
+        and `root` change in place.  Duplicate indices are sequential updates (the last one wins); an index >= n_leaves is a PmxError
+        and nothing changes."""
+        if not (self.nodes.dtype == np.uint64 and self.nodes.flags["C_CONTIGUOUS"] and self.nodes.flags["WRITEABLE"]):
+            self.nodes = np.array(self.nodes, dtype=np.uint64, order="C")
+        root = self.parameters.context(self.device).merkle_ary_update(self.nodes, self.n_leaves, self.arity, leaf_indices, leaves)
+        self._root[...] = root
+
     def paths_dev(self, leaf_indices) -> np.ndarray:
         """paths() through the device-side gather (pmx_merkle_ary_paths_dev): node array and indices are uploaded, the paths
         gathered there and downloaded.  (A caller whose node array already lives on the device calls

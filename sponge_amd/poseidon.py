@@ -351,6 +351,25 @@ class Context:
         """d_work: [k][(arity + 1) * 4] u64 of scratch; d_ok: k bytes at any address."""
         _lib.check(_lib.lib().pmx_merkle_ary_verify_paths_dev(self._h, d_leaves, d_indices, d_paths, depth, arity, k, d_root, d_ok, d_work, stream))
 
+    def merkle_ary_update(self, nodes: np.ndarray, n_leaves: int, arity: int, indices, new_leaves) -> np.ndarray:
+        """Replace leaves indices[i] of the node array `nodes` [n_nodes][4] (C-contiguous uint64, changed in place) by new_leaves[i] and
+        recompute their ancestors only (pmx_merkle_ary_update).  Duplicates are sequential updates: the last one wins.  Returns the
+        new root."""
+        assert nodes.dtype == np.uint64 and nodes.flags["C_CONTIGUOUS"] and nodes.flags["WRITEABLE"], "nodes is updated in place"
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        new = np.ascontiguousarray(new_leaves, dtype=np.uint64).reshape(-1, 4)
+        assert new.shape[0] == idx.shape[0], "one new leaf per index"
+        root = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_merkle_ary_update(self._h, _ptr(nodes), n_leaves, arity, _ptr(idx) if idx.size else None,
+                                                    _ptr(new) if idx.size else None, idx.shape[0], _ptr(root)))
+        return root
+
+    def merkle_ary_update_dev(self, d_nodes: int, n_leaves: int, arity: int, d_indices: int, d_new_leaves: int, k: int, d_work: int,
+                              stream: int = 0) -> None:
+        """the same on a device-resident node array, enqueue only; d_work: [k][(arity + 1) * 4] u64 of scratch.  An index >= n_leaves is
+        ignored."""
+        _lib.check(_lib.lib().pmx_merkle_ary_update_dev(self._h, d_nodes, n_leaves, arity, d_indices, d_new_leaves, k, d_work, stream))
+
     # ---- device-pointer entry points (only enqueue; pointers are raw device addresses) ---------
     def permute_batch_dev(self, d_states: int, n: int, stream: int = 0) -> None:
         _lib.check(_lib.lib().pmx_permute_batch_dev(self._h, d_states, n, stream))
