@@ -135,6 +135,22 @@ extern "C" {
                                      d_new_leaves: *const u64, k: usize, d_work: *mut u64, stream: *mut c_void) -> c_int;
     pub fn pmx_merkle_ary_update(ctx: *mut pmx_ctx, nodes: *mut u64, n_leaves: usize, arity: u32, indices: *const u64,
                                  new_leaves: *const u64, k: usize, root: *mut u64) -> c_int;
+    // trees over any number of leaves: level l + 1 has ceil(M_l / arity) nodes, a short parent absorbs the children that exist; the root
+    // does not bind n_leaves, so verification takes it (declarations only: the safe wrappers of mod.rs cover the arity^depth trees)
+    pub fn pmx_merkle_ragged_shape(n_leaves: usize, arity: u32, depth: *mut usize, n_nodes: *mut usize) -> c_int;
+    pub fn pmx_merkle_ragged(ctx: *mut pmx_ctx, leaves: *const u64, n_leaves: usize, arity: u32, nodes: *mut u64, root: *mut u64) -> c_int;
+    pub fn pmx_merkle_ragged_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_leaves: usize, arity: u32, stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ragged_paths(nodes: *const u64, n_leaves: usize, arity: u32, indices: *const u64, k: usize,
+                                   paths_out: *mut u64) -> c_int;
+    pub fn pmx_merkle_ragged_paths_dev(ctx: *mut pmx_ctx, d_nodes: *const u64, n_leaves: usize, arity: u32, d_indices: *const u64,
+                                       k: usize, d_paths: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ragged_verify_paths(ctx: *mut pmx_ctx, leaves: *const u64, indices: *const u64, paths: *const u64, depth: usize,
+                                          arity: u32, n_leaves: usize, k: usize, root: *const u64, ok_out: *mut u8) -> c_int;
+    pub fn pmx_merkle_ragged_verify_paths_dev(ctx: *mut pmx_ctx, d_leaves: *const u64, d_indices: *const u64, d_paths: *const u64,
+                                              depth: usize, arity: u32, n_leaves: usize, k: usize, d_root: *const u64, d_ok: *mut u8,
+                                              d_work: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn pmx_merkle_ragged_update_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_leaves: usize, arity: u32, d_indices: *const u64,
+                                        d_new_leaves: *const u64, k: usize, d_work: *mut u64, stream: *mut c_void) -> c_int;
     // device memory for the *_dev entry points
     pub fn pmx_device_alloc(device: c_int, d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_device_free(device: c_int, d_ptr: *mut c_void) -> c_int;

@@ -385,6 +385,55 @@ int pmx_merkle_ary_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, 
 int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices,
                           const uint64_t *new_leaves, size_t k, uint64_t *root /* may be NULL */);
 
+/* ---- Merkle trees over any number of leaves -----------------------------------------------------------
+ * pmx_merkle_ary* takes arity^depth leaves only; people commit to 2^k rows, or to however many they have.  For 2 <= arity <= rate and any
+ * n_leaves >= 1: level 0 is the leaves (M_0 = n_leaves), level l + 1 has M_{l+1} = ceil(M_l / arity) nodes, and the first level of width
+ * 1 is the root; depth = the levels above the leaves (n_leaves = 1: depth 0, the leaf is the root, nothing is launched).  Parent p of
+ * level l + 1 absorbs the children p * arity .. min((p + 1) * arity, M_l) - 1 of level l:
+ *   parent = (new; absorb(the r <= arity children that exist); squeeze_native(1))[0]
+ *          = permute(state[capacity + j] = c_j for j < r, every other element 0)[capacity],
+ * the reference sponge's own answer for a short row - absorb takes any number of elements, and at most `rate` of them into a fresh sponge
+ * permute once, at the squeeze (src/poseidon/mod.rs:126-135, 219-230, 324-328).  A parent with ONE child is still a permutation, not a
+ * promotion of the child.  (No counterpart in the reference.)
+ * What the root does NOT bind: a short parent equals the parent of the same children padded with zero elements, so the root does not
+ *   commit to n_leaves - the tree over n leaves and the tree over the same leaves followed by zero leaves up to the end of the last
+ *   parent's row have one root.  A caller who needs the length bound binds it itself (in a leaf, or next to the root); verification
+ *   takes n_leaves for this reason and accepts no index at or above it.
+ * nodes: [n_nodes][4] as everywhere - the leaves, then every level, root last; n_nodes = sum of the M_l, level l starts at row
+ *   M_0 + ... + M_{l-1}.  pmx_merkle_ragged_shape (host only) gives depth and n_nodes and refuses arity < 2, n_leaves = 0 and a node
+ *   array whose byte size overflows size_t (PMX_ERR_ARG).  At n_leaves = arity^depth every array of this family is byte for byte what
+ *   pmx_merkle_ary* produces and accepts and the same launches run; at arity 2 and a power of two the same holds for pmx_merkle_2to1*.
+ * pmx_merkle_ragged: host buffers; nodes / root may be NULL.  pmx_merkle_ragged_dev: d_nodes holds the leaves in its first n_leaves rows;
+ *   it only enqueues and allocates nothing (it may be captured like pmx_merkle_ary_dev): ONE compression launch per level, on the engine
+ *   pmx_ctx_engine_info(ctx, PMX_OP_COMPRESS, W, arity) names for the level's W = M_{l+1} parents - at arity 2 too, the quad engine
+ *   included; the short last row is bounded inside that launch and nothing at or beyond the level's end is read.
+ * Paths: [k][depth][arity - 1][4] as for pmx_merkle_ary_paths; a sibling that does not exist (its index is at or beyond its level's
+ *   width) is four zero words.  pmx_merkle_ragged_paths: host-only gather, an index >= n_leaves is PMX_ERR_ARG and nothing is written.
+ *   pmx_merkle_ragged_paths_dev: the gather on the device, enqueue only; an index >= n_leaves gets an all-zero path.
+ * Verification: ok[i] = 1 iff hashing leaves[i] up its path gives `root` AND indices[i] < n_leaves.  The climb is that of
+ *   pmx_merkle_ary_verify_paths* (absent siblings are zeros, so every row is a full one); d_work is [k][(arity + 1) * 4] u64.  depth must
+ *   be the depth of (n_leaves, arity): PMX_ERR_ARG otherwise.
+ * pmx_merkle_ragged_update_dev: the contract of pmx_merkle_ary_update_dev - enqueue only, nothing allocated, the same d_work, indices
+ *   >= n_leaves ignored, whole-level launches from the first level with k >= W parents on; afterwards the array is byte for byte what a
+ *   rebuild over the new leaves gives.  (There is no host-array pmx_merkle_ragged_update, no ragged forest and no device-group form.)
+ * Errors, nothing launched or written on any: PMX_ERR_ARG for arity < 2, n_leaves = 0, byte sizes that overflow, a depth that is not the
+ *   tree's, null pointers, an element array that is not 16-byte aligned (d_indices needs 8 bytes, d_ok any address), "batch too large" by
+ *   the bounds of pmx_merkle_ary_verify_paths_dev; PMX_ERR_CONFIG for arity > rate. */
+int pmx_merkle_ragged_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes);
+int pmx_merkle_ragged(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root);
+int pmx_merkle_ragged_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream);
+int pmx_merkle_ragged_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
+                            uint64_t *paths_out);
+int pmx_merkle_ragged_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                size_t k, uint64_t *d_paths, void *stream);
+int pmx_merkle_ragged_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                   uint32_t arity, size_t n_leaves, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out);
+int pmx_merkle_ragged_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                       size_t depth, uint32_t arity, size_t n_leaves, size_t k, const uint64_t *d_root, uint8_t *d_ok,
+                                       uint64_t *d_work, void *stream);
+int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                 const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream);
+
 /* ---- device groups: the batch sharded over the GPUs of one node -------------------------------------
  * The reference is single-threaded and has no distributed code; nothing in src/poseidon/mod.rs:62-183 couples one
  * sponge state to another, so n states are cut into `world` contiguous shards (pmx_shard_bounds), one per GPU, and

@@ -151,6 +151,17 @@ SIGNATURES = {
                                                        _u64p, ctypes.c_void_p]),
     "pmx_merkle_ary_update": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _u64p, _sz, _u64p]),
     "pmx_merkle_ary_update_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _u64p, _sz, _u64p, ctypes.c_void_p]),
+    # trees over any number of leaves
+    "pmx_merkle_ragged_shape": (ctypes.c_int, [_sz, ctypes.c_uint32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "pmx_merkle_ragged": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _u64p]),
+    "pmx_merkle_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, ctypes.c_void_p]),
+    "pmx_merkle_ragged_paths": (ctypes.c_int, [_u64p, _sz, ctypes.c_uint32, _u64p, _sz, _u64p]),
+    "pmx_merkle_ragged_paths_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _sz, _u64p, ctypes.c_void_p]),
+    "pmx_merkle_ragged_verify_paths": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, ctypes.c_uint32, _sz, _sz, _u64p,
+                                                      ctypes.c_void_p]),
+    "pmx_merkle_ragged_verify_paths_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, ctypes.c_uint32, _sz, _sz, _u64p,
+                                                          ctypes.c_void_p, _u64p, ctypes.c_void_p]),
+    "pmx_merkle_ragged_update_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _u64p, _sz, _u64p, ctypes.c_void_p]),
     # device groups
     "pmx_shard_bounds": (ctypes.c_int, [_sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "pmx_mgpu_unique_id": (ctypes.c_int, [ctypes.c_void_p]),

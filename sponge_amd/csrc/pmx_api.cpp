@@ -1303,13 +1303,9 @@ extern "C" int pmx_merkle_ary_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, s
 // pmx_merkle_verify_paths_dev for any arity: per level a gather kernel lays the arity children of every path's parent out as the rows
 // one tree level has, and the compression launcher of that arity writes the parents back into cur.
 // d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).
-extern "C" int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
-                                               size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
-                                               void *stream) {
-    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths_dev: null pointer");
-    uint64_t n_leaves = 0;
-    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
+// (the level loop behind the entry's own checks, shared with pmx_merkle_ragged_verify_paths_dev: `limit` is what an index must stay below)
+static int ary_verify_levels_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths, size_t depth,
+                                 uint32_t arity, uint64_t limit, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream) {
     if (int rc = arity_fits(ctx, arity)) return rc;
     if (k == 0) return PMX_OK;
     // (depth <= 64 and arity <= PMX_MAX_WIDTH here: the products below stay small)
@@ -1325,18 +1321,22 @@ extern "C" int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_l
         PMX_HIP(launch_path_children(cur, d_paths, d_indices, depth, level, pow, arity, rows, k, st));
         PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
     }
-    PMX_HIP(launch_path_check(cur, d_root, d_indices, n_leaves, d_ok, k, st));
+    PMX_HIP(launch_path_check(cur, d_root, d_indices, limit, d_ok, k, st));
     return PMX_OK;
+}
+extern "C" int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                               size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
+                                               void *stream) {
+    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths_dev: null pointer");
+    uint64_t n_leaves = 0;
+    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
+    return ary_verify_levels_dev(ctx, d_leaves, d_indices, d_paths, depth, arity, n_leaves, k, d_root, d_ok, d_work, stream);
 }
 
 // Host buffers: one upload of (leaves, indices, paths, root), `depth` level steps on the device, one download of ok.
-extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
-                                           uint32_t arity, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
-    PMX_ABI_BEGIN("pmx_merkle_ary_verify_paths")
-    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths: null pointer");
-    uint64_t n_leaves = 0;
-    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
+static int ary_verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth, uint32_t arity,
+                           uint64_t limit, size_t k, const uint64_t *root, uint8_t *ok_out) {
     if (int rc = arity_fits(ctx, arity)) return rc;
     if (k == 0) return PMX_OK;
     if (k > (SIZE_MAX / 64) / (arity + 2) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
@@ -1357,11 +1357,20 @@ extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves,
     if (path_bytes) PMX_HIP(hipMemcpyAsync(d1, paths, path_bytes, hipMemcpyHostToDevice, ctx->stream));
     PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
     PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pmx_merkle_ary_verify_paths_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, k, d_root, (uint8_t *)d3, d_work, ctx->stream)))
+    if ((rc = ary_verify_levels_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, limit, k, d_root, (uint8_t *)d3, d_work, ctx->stream)))
         return rc;
     PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
+}
+extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                           uint32_t arity, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_verify_paths")
+    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths: null pointer");
+    uint64_t n_leaves = 0;
+    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
+    return ary_verify_host(ctx, leaves, indices, paths, depth, arity, n_leaves, k, root, ok_out);
     PMX_ABI_END
 }
 
@@ -1444,4 +1453,168 @@ extern "C" int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_lea
     if (root) std::memcpy(root, nodes + (n_nodes - 1) * 4, 32);
     return PMX_OK;
     PMX_ABI_END
+}
+
+// ---- trees over any number of leaves ----------------------------------------------------------------------------------------------
+// The layouts of pmx_merkle_ary* with level l + 1 of ceil(M_l / arity) nodes: the last parent of a level that does not divide absorbs the
+// r < arity children that exist, (new; absorb(r elements); squeeze_native(1))[0] - one permutation of [0, c_0 .. c_{r-1}, 0 ..]
+// (mod.rs:126-135, 219-230, 324-328).  At n_leaves = arity^depth every level divides and every launch is the one pmx_merkle_ary* makes.
+static int ragged_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
+    if (arity < 2) return set_error(PMX_ERR_ARG, "arity must be at least 2");
+    if (n_leaves == 0) return set_error(PMX_ERR_ARG, "a tree needs at least one leaf");
+    size_t d = 0, nodes = 0;
+    for (size_t width = n_leaves;; width = width / arity + (width % arity ? 1 : 0), ++d) {
+        if (width > SIZE_MAX / 32 - nodes) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
+        nodes += width;
+        if (width == 1) break;
+    }
+    *depth = d;
+    *n_nodes = nodes;
+    return PMX_OK;
+}
+// every level from the one of `width` nodes at `first` up to the root: one compression launch per level
+static int ragged_levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t first, size_t width, uint32_t arity, hipStream_t st) {
+    while (width > 1) {
+        PMX_HIP(launch_compress_level(ctx->dev, ctx->t, d_nodes + first * 4, d_nodes + (first + width) * 4, arity, width, st));
+        first += width;
+        width = width / arity + (width % arity ? 1 : 0);
+    }
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_ragged_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
+    if (!depth || !n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_shape: null pointer");
+    return ragged_shape(n_leaves, arity, depth, n_nodes);
+}
+
+extern "C" int pmx_merkle_ragged_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_dev: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (!aligned16(d_nodes)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    PMX_BIND(ctx);
+    return ragged_levels_dev(ctx, d_nodes, 0, n_leaves, arity, (hipStream_t)stream);
+}
+
+extern "C" int pmx_merkle_ragged(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_ragged")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    int rc = PMX_OK;
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    void *d = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d, leaves, n_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ragged_levels_dev(ctx, (uint64_t *)d, 0, n_leaves, arity, ctx->stream))) return rc;
+    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (root) PMX_HIP(hipMemcpyAsync(root, (uint64_t *)d + (n_nodes - 1) * 4, 32, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// openings: the shape of pmx_merkle_ary_paths; a sibling at or beyond its level's width does not exist and is four zero words
+extern "C" int pmx_merkle_ragged_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
+                                       uint64_t *paths_out) {
+    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_paths: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    for (size_t i = 0; i < k; ++i)     // (before anything is written)
+        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
+    const size_t sib = arity - 1;
+    for (size_t i = 0; i < k; ++i) {
+        size_t idx = (size_t)indices[i], first = 0, width = n_leaves;   // first node of the current level, its width
+        for (size_t level = 0; level < depth; ++level) {
+            const size_t digit = idx % arity, base = idx - digit;
+            uint64_t *row = paths_out + (i * depth + level) * sib * 4;
+            for (size_t s = 0; s < sib; ++s) {
+                const size_t child = base + (s < digit ? s : s + 1);
+                if (child < width) std::memcpy(row + s * 4, nodes + (first + child) * 4, 32);
+                else std::memset(row + s * 4, 0, 32);
+            }
+            first += width;
+            width = width / arity + (width % arity ? 1 : 0);
+            idx /= arity;
+        }
+    }
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_ragged_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                           size_t k, uint64_t *d_paths, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_paths_dev: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0 || depth == 0) return PMX_OK;
+    const size_t per = depth * (arity - 1);     // elements per path (depth <= 64, arity <= PMX_MAX_WIDTH)
+    if (k > (SIZE_MAX / 32) / per || k > ((size_t)0x7fffffff * 64) / per) return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_nodes) || !aligned16(d_paths)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    PMX_BIND(ctx);
+    PMX_HIP(launch_paths_gather_ragged(d_nodes, n_leaves, arity, depth, d_indices, d_paths, k, (hipStream_t)stream));
+    return PMX_OK;
+}
+
+// The climb is pmx_merkle_ary_verify_paths*'s own - an absent sibling is the zero a short parent's rate lane holds - with the tree's
+// leaf count as the limit of the indices: the root does not bind n_leaves, so the caller states it, and depth must be its depth.
+static int ragged_verify_shape(size_t depth, uint32_t arity, size_t n_leaves) {
+    size_t d = 0, n_nodes = 0;
+    if (int rc = ragged_shape(n_leaves, arity, &d, &n_nodes)) return rc;
+    if (d != depth) return set_error(PMX_ERR_ARG, "depth %zu is not the depth %zu of a tree of arity %u over %zu leaves", depth, d, arity, n_leaves);
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_ragged_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                                  size_t depth, uint32_t arity, size_t n_leaves, size_t k, const uint64_t *d_root,
+                                                  uint8_t *d_ok, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths_dev: null pointer");
+    if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
+    return ary_verify_levels_dev(ctx, d_leaves, d_indices, d_paths, depth, arity, (uint64_t)n_leaves, k, d_root, d_ok, d_work, stream);
+}
+
+extern "C" int pmx_merkle_ragged_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                              uint32_t arity, size_t n_leaves, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
+    PMX_ABI_BEGIN("pmx_merkle_ragged_verify_paths")
+    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths: null pointer");
+    if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
+    return ary_verify_host(ctx, leaves, indices, paths, depth, arity, (uint64_t)n_leaves, k, root, ok_out);
+    PMX_ABI_END
+}
+
+// pmx_merkle_ary_update_dev with the level widths as ceilings: the gather zero-fills the children a short parent does not have (the row
+// is then the full row launch_compress_ary takes), the scatter is the same - index / arity^(l+1) is the ancestor's index, floor division
+// nests - and the whole levels from the first one with k >= W on are the builder's launches.
+extern "C" int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                            const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_new_leaves || !d_work) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_update_dev: null pointer");
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
+    if (!aligned16(d_nodes) || !aligned16(d_new_leaves) || !aligned16(d_work)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
+    PMX_BIND(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *cur = d_work, *rows = d_work + k * 4;
+    PMX_HIP(launch_node_scatter(d_new_leaves, d_indices, 1, n_leaves, 0, d_nodes, k, st));
+    size_t first = 0, width = n_leaves;      // level l: its first node, its width
+    uint64_t pow = arity;                    // arity^(l+1) (below n_leaves * arity: no overflow)
+    for (size_t l = 0; l < depth; ++l, pow *= arity) {
+        const size_t parents = width / arity + (width % arity ? 1 : 0);
+        if (k >= parents) return ragged_levels_dev(ctx, d_nodes, first, width, arity, st);     // the rest of the tree as whole levels
+        PMX_HIP(launch_node_children_bounded(d_nodes, d_indices, pow, n_leaves, first, width, arity, rows, k, st));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
+        PMX_HIP(launch_node_scatter(cur, d_indices, pow, n_leaves, first + width, d_nodes, k, st));
+        first += width;
+        width = parents;
+    }
+    return PMX_OK;
 }

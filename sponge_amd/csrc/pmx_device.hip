@@ -780,6 +780,35 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
 }
 
+// The same for a level whose last row is short (pmx_merkle_ragged*: a level of n_children nodes that is no multiple of the arity, or of
+// the rate at arity 2): a bounded twin of compress_ary_kernel, as RowsRagged is of RowsFixed - parent gid absorbs the children
+// gid * arity .. min((gid + 1) * arity, n_children) - 1 and loads nothing at or beyond n_children (the rows behind the level are the next
+// level's nodes, which this very launch writes).  The rate lanes of the children that do not exist keep the zeros of e.zero(): the state of
+// (new; absorb(the r children that exist)), mod.rs:126-135 - still one permutation.  The bound is a predicate on the rolled child loop, so
+// the loop's trip count stays wave-uniform; it serves every arity, 2 included (the quad engine: a quad shares its unit, so its `have`).
+// A level that divides by the arity never comes here (launch_compress_level): the full-row kernels above are what they were.
+template <class Engine>
+__global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
+    compress_ary_bounded_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ in, uint32_t arity,
+                                size_t n_children, uint64_t *__restrict__ out, size_t n) {
+    Engine e(d, consts);
+    const size_t gid = Engine::unit();
+    const bool active = gid < n;
+    const size_t first = (active ? gid : 0) * (size_t)arity;
+    // children this parent has: arity, fewer for the last parent, none for a lane that is no parent
+    const uint32_t have = active && first < n_children ? (n_children - first < (size_t)arity ? (uint32_t)(n_children - first) : arity) : 0;
+    const uint32_t *row = reinterpret_cast<const uint32_t *>(in + first * 4);
+    e.zero();
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 0; j < arity; ++j) {
+        const uint32_t at = e.c.capacity + j;
+        if (j < have && e.owns(at)) e.set(at, e.from_abi(abi_load(row + 8 * j)));
+    }
+    e.permute(e.c.capacity, e.c.capacity + 1, e.c.capacity >= 1);   // only the digest lane of the result is read; lane 0 (capacity) went in as zero
+    const Abi digest = e.to_abi(e.get(e.c.capacity));
+    if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
+}
+
 // (per-lane engines: every lane keeps its own cursor and length - lanes of a wave may absorb rows of different lengths; a lane whose
 // row is empty absorbs nothing and leaves its mode words alone, mod.rs:234-236)
 template <class Engine, class Rows>
@@ -1029,6 +1058,13 @@ struct Launch {
                            c.consts, in, arity, out, n);
         return hipGetLastError();
     }
+    static hipError_t compress_ary_bounded(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
+                                           size_t n, hipStream_t st) {
+        allow_lds(compress_ary_bounded_kernel<Engine>, Engine::lds_bytes(c, t));
+        hipLaunchKernelGGL(compress_ary_bounded_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                           c.consts, in, arity, n_children, out, n);
+        return hipGetLastError();
+    }
     // absorb / squeeze: per-lane kernels, or - on an engine whose permutation must stay wave-uniform - passes on its permutation
     // (pmx_sponge_plan.hpp).  Only the form the engine has is instantiated.
     template <class Rows>
@@ -1123,7 +1159,7 @@ struct Launch {
 template <class Engine>
 static const EngineOps &engine_ops() {
     using L = Launch<Engine>;
-    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::compress_ary, &L::absorb, &L::absorb_varlen, &L::squeeze,
+    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::compress_ary, &L::compress_ary_bounded, &L::absorb, &L::absorb_varlen, &L::squeeze,
                                       &Engine::lds_bytes, &L::describe};
     return ops;
 }
@@ -1231,6 +1267,16 @@ hipError_t launch_compress_ary(const DevConfig &c, uint32_t t, const uint64_t *i
     if (arity < 2 || arity > c.rounds.rate) return hipErrorInvalidValue;
     if (arity == 2) return launch_compress(c, t, in, out, n, st);
     return select_engine(c, t, PMX_OP_COMPRESS, n)->compress_ary(c, t, in, out, arity, n, st);
+}
+// One tree level of n_children nodes, any number of them (pmx_merkle_ragged*): ceil(n_children / arity) parents in ONE launch on the engine
+// the choice names for that many parents, the quad engine included.  A level that divides by the arity is launch_compress_ary, launch
+// for launch; only a level with a short last row runs the bounded twin, at arity 2 too - never a second launch for the odd child.
+hipError_t launch_compress_level(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
+                                 hipStream_t st) {
+    if (arity < 2 || arity > c.rounds.rate || n_children == 0) return hipErrorInvalidValue;
+    const size_t n = n_children / arity + (n_children % arity ? 1 : 0);
+    if (n_children % arity == 0) return launch_compress_ary(c, t, in, out, arity, n, st);
+    return select_engine(c, t, PMX_OP_COMPRESS, n)->compress_ary_bounded(c, t, in, out, arity, n_children, n, st);
 }
 hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch) {
@@ -1361,6 +1407,57 @@ __global__ void __launch_bounds__(256) node_children_kernel(const uint4 *__restr
     if (i >= k) return;
     const uint64_t idx = indices[i], p = idx < n_leaves ? idx / pow : 0;
     rows[gid] = nodes[(first + p * arity) * 2 + (gid - i * per)];
+}
+
+// ---- trees over any number of leaves (pmx_merkle_ragged*) -------------------------------------------------------------------------------
+// Level l + 1 has ceil(M_l / arity) nodes, so a level's width and first row are carried down the levels, not divided out.  Bounded twins of
+// paths_gather_kernel and node_children_kernel: a child at or beyond its level's width does not exist - it is four zero words in the
+// opening and in the gathered row (the zero a short parent's rate lane holds), and nothing at or beyond the level's end is read.
+__global__ void __launch_bounds__(256) paths_gather_ragged_kernel(const uint4 *__restrict__ nodes, uint64_t n_leaves, uint32_t arity, size_t depth,
+                                                                  const uint64_t *__restrict__ indices, uint4 *__restrict__ paths, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per_level = 2 * (size_t)(arity - 1), per = depth * per_level, i = gid / per;
+    if (i >= k) return;
+    const size_t rest = gid - i * per, level = rest / per_level;
+    const uint32_t quarter = (uint32_t)(rest - level * per_level), sibling = quarter >> 1, half = quarter & 1;
+    uint64_t idx = indices[i], first = 0, width = n_leaves;   // the running node's index in its level, the level's first node, its width
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (idx < n_leaves) {
+        for (size_t l = 0; l < level; ++l) {
+            first += width;
+            width = width / arity + (width % arity ? 1 : 0);
+            idx /= arity;
+        }
+        const uint32_t digit = (uint32_t)(idx % arity);
+        const uint64_t child = (idx - digit) + (sibling < digit ? sibling : sibling + 1);   // in its level
+        if (child < width) v = nodes[(first + child) * 2 + half];
+    }
+    paths[gid] = v;
+}
+
+// `width`: the nodes level l has (its first node is `first`); parent p = indices[i] / pow has the children p * arity .. below width
+__global__ void __launch_bounds__(256) node_children_bounded_kernel(const uint4 *__restrict__ nodes, const uint64_t *__restrict__ indices,
+                                                                    uint64_t pow, uint64_t n_leaves, uint64_t first, uint64_t width,
+                                                                    uint32_t arity, uint4 *__restrict__ rows, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per = 2 * (size_t)arity, i = gid / per;
+    if (i >= k) return;
+    const uint32_t quarter = (uint32_t)(gid - i * per), half = quarter & 1;
+    const uint64_t idx = indices[i], p = idx < n_leaves ? idx / pow : 0, child = p * arity + (quarter >> 1);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (child < width) v = nodes[(first + child) * 2 + half];
+    rows[gid] = v;
+}
+
+hipError_t launch_paths_gather_ragged(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices,
+                                      uint64_t *paths, size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(paths_gather_ragged_kernel, dim3((unsigned)((k * depth * 2 * (arity - 1) + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const uint4 *>(nodes), (uint64_t)n_leaves, arity, depth, indices, reinterpret_cast<uint4 *>(paths), k);
+    return hipGetLastError();
+}
+hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first,
+                                        uint64_t width, uint32_t arity, uint64_t *rows, size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(node_children_bounded_kernel, dim3((unsigned)((k * 2 * arity + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const uint4 *>(nodes), indices, pow, n_leaves, first, width, arity, reinterpret_cast<uint4 *>(rows), k);
+    return hipGetLastError();
 }
 
 hipError_t launch_node_scatter(const uint64_t *src, const uint64_t *indices, uint64_t pow, uint64_t limit, uint64_t base, uint64_t *dst,

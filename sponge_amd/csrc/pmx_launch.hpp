@@ -18,6 +18,11 @@ hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
 // out[i] = arity-to-1 compression of in[arity i .. arity i + arity)   (2 <= arity <= rate; arity 2 is launch_compress)
 hipError_t launch_compress_ary(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st);
+// one tree level of n_children nodes, any number >= 1 (pmx_merkle_ragged*): out[p] = the compression of in[arity p .. min(arity (p + 1),
+// n_children)) for the ceil(n_children / arity) parents, in one launch; nothing at or beyond in[n_children] is read.  A level that divides
+// by the arity is launch_compress_ary.
+hipError_t launch_compress_level(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
+                                 hipStream_t st);
 // Device scratch for the pass lists of the drivers that run as passes (pmx_device.hip: sponge_passes): `get` hands out at least
 // `bytes` bytes that stay valid for everything enqueued on `st` by this call, `done` is called once behind the call's last launch
 // (pmx_api.cpp: a pool of blocks owned by the context, each released by an event recorded there).  Engines that need no lists
@@ -58,6 +63,9 @@ struct EngineOps {
                        hipStream_t st);
     hipError_t (*compress)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
     hipError_t (*compress_ary)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st);
+    // (the level with a short last row: n = ceil(n_children / arity) parents, children bounded by n_children)
+    hipError_t (*compress_ary_bounded)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
+                                       size_t n, hipStream_t st);
     hipError_t (*absorb)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
                          size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch);
     hipError_t (*absorb_varlen)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
@@ -89,5 +97,11 @@ hipError_t launch_node_scatter(const uint64_t *src, const uint64_t *indices, uin
                                size_t k, hipStream_t st);
 hipError_t launch_node_children(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first, uint32_t arity,
                                 uint64_t *rows, size_t k, hipStream_t st);
+// Trees over any number of leaves (pmx_merkle_ragged*): the two gathers with the level's width carried along - a child at or beyond it is
+// four zero words, and nothing at or beyond the level's end is read.  `width`: the nodes of the level whose first node is `first`.
+hipError_t launch_paths_gather_ragged(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices,
+                                      uint64_t *paths, size_t k, hipStream_t st);
+hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first,
+                                        uint64_t width, uint32_t arity, uint64_t *rows, size_t k, hipStream_t st);
 
 }  // namespace pmx

@@ -14,7 +14,7 @@ import numpy as np
 import ctypes
 
 from . import _lib
-from .poseidon import PoseidonConfig, merkle_ary_shape
+from .poseidon import PoseidonConfig, merkle_ragged_shape
 
 
 class MerkleTree:
@@ -22,17 +22,19 @@ class MerkleTree:
         leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
         m = leaves.shape[0]
         assert arity >= 2, "a parent has at least two children"
-        if arity == 2:
-            assert m >= 1 and (m & (m - 1)) == 0, "number of leaves must be a power of two"
-            self.depth = m.bit_length() - 1
-        else:
-            self.depth, _ = merkle_ary_shape(m, arity)     # PmxError: the number of leaves must be a power of the arity
+        assert m >= 1, "a tree has at least one leaf"
+        # any leaf count: every level has ceil(width / arity) parents, the last one absorbs the children that exist (pmx_merkle_ragged);
+        # a power of the arity is the tree it always was
+        self.depth, _ = merkle_ragged_shape(m, arity)
+        self.ragged = m != arity ** self.depth
         self.parameters = parameters
         self.device = device
         self.arity = arity
         self.n_leaves = m
         if m == 1:
             self.nodes, self._root = leaves.copy(), leaves[0].copy()
+        elif self.ragged:
+            self.nodes, self._root = parameters.context(device).merkle_ragged(leaves, arity)
         elif arity == 2:
             self.nodes, self._root = parameters.context(device).merkle_2to1(leaves)
         else:
@@ -42,12 +44,20 @@ class MerkleTree:
     def root(self) -> np.ndarray:
         return self._root
 
+    def level_widths(self) -> List[int]:
+        """nodes per level, leaves first: n, ceil(n / arity), ..., 1"""
+        widths = [self.n_leaves]
+        while widths[-1] > 1:
+            widths.append(-(-widths[-1] // self.arity))
+        return widths
+
     def level_offset(self, level: int) -> int:
-        """Index of the first node of `level` (0 = leaves) in `nodes`: n + n / arity + ... + n / arity^(level - 1)."""
-        return sum(self.n_leaves // self.arity ** l for l in range(level))
+        """Index of the first node of `level` (0 = leaves) in `nodes`: the widths of the levels below it, n + ceil(n / arity) + ..."""
+        return sum(self.level_widths()[:level])
 
     def path(self, leaf_index: int) -> np.ndarray:
-        """Siblings of the leaf, then of each ancestor, bottom-up: [depth][4] (arity 2), [depth][arity - 1][4] otherwise."""
+        """Siblings of the leaf, then of each ancestor, bottom-up: [depth][4] (arity 2), [depth][arity - 1][4] otherwise.  In a tree
+        whose leaf count is no power of the arity a sibling that does not exist is four zero words."""
         assert 0 <= leaf_index < self.n_leaves
         return self.paths([leaf_index])[0]
 
@@ -60,7 +70,10 @@ class MerkleTree:
         idx = np.ascontiguousarray(leaf_indices, dtype=np.uint64)
         out = np.zeros(self._path_shape(idx.shape[0]), dtype=np.uint64)
         nodes = np.ascontiguousarray(self.nodes, dtype=np.uint64)
-        if self.arity == 2:
+        if self.ragged:
+            _lib.check(_lib.lib().pmx_merkle_ragged_paths(ctypes.c_void_p(nodes.ctypes.data), self.n_leaves, self.arity,
+                                                          ctypes.c_void_p(idx.ctypes.data), idx.shape[0], ctypes.c_void_p(out.ctypes.data)))
+        elif self.arity == 2:
             _lib.check(_lib.lib().pmx_merkle_paths(ctypes.c_void_p(nodes.ctypes.data), self.n_leaves, ctypes.c_void_p(idx.ctypes.data),
                                                    idx.shape[0], ctypes.c_void_p(out.ctypes.data)))
         else:
@@ -74,8 +87,51 @@ class MerkleTree:
         and nothing changes."""
         if not (self.nodes.dtype == np.uint64 and self.nodes.flags["C_CONTIGUOUS"] and self.nodes.flags["WRITEABLE"]):
             self.nodes = np.array(self.nodes, dtype=np.uint64, order="C")
+        if self.ragged:
+            return self._update_ragged(leaf_indices, leaves)
         root = self.parameters.context(self.device).merkle_ary_update(self.nodes, self.n_leaves, self.arity, leaf_indices, leaves)
         self._root[...] = root
+
+    def _with_device_blocks(self, arrays, run, download):
+        """upload `arrays` (None: an uninitialised block of that many bytes), run(pointers), download {block number: host array}"""
+        L, dev = _lib.lib(), self.device
+        blocks: List[ctypes.c_void_p] = []
+        try:
+            for a in arrays:
+                d = ctypes.c_void_p()
+                _lib.check(L.pmx_device_alloc(dev, ctypes.byref(d), a if isinstance(a, int) else a.nbytes))
+                blocks.append(d)
+                if not isinstance(a, int):
+                    _lib.check(L.pmx_device_upload(dev, d, ctypes.c_void_p(a.ctypes.data), a.nbytes, None))
+            run(blocks)
+            for number, out in download.items():
+                _lib.check(L.pmx_device_download(dev, ctypes.c_void_p(out.ctypes.data), blocks[number], out.nbytes, None))
+            _lib.check(L.pmx_stream_synchronize(dev, None))
+        finally:
+            for d in blocks:
+                L.pmx_device_free(dev, d)
+
+    def _update_ragged(self, leaf_indices, leaves) -> None:
+        """update() of a tree whose leaf count is no power of the arity: the node array goes to the device, pmx_merkle_ragged_update_dev
+        runs there and the array comes back (there is no host-array entry for this layout).  The device entry ignores an index >=
+        n_leaves and leaves duplicates unordered, so both are settled here: a bad index is a PmxError, the last duplicate wins."""
+        idx = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+        new = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        assert new.shape[0] == idx.shape[0], "one new leaf per index"
+        bad = idx[idx >= np.uint64(self.n_leaves)]
+        if bad.size:
+            raise _lib.PmxError(_lib.PMX_ERR_ARG, f"leaf index {int(bad[0])} out of range")
+        if idx.size == 0:
+            return
+        last = {int(i): n for n, i in enumerate(idx)}                  # index -> its last update
+        keep = np.array(sorted(last.values()), dtype=np.int64)
+        idx, new = np.ascontiguousarray(idx[keep]), np.ascontiguousarray(new[keep])
+        k, ctx = idx.shape[0], self.parameters.context(self.device)
+        self._with_device_blocks(
+            [self.nodes, idx, new, k * (self.arity + 1) * 32],
+            lambda d: ctx.merkle_ragged_update_dev(d[0], self.n_leaves, self.arity, d[1], d[2], k, d[3], None),
+            {0: self.nodes})
+        self._root[...] = self.nodes[-1]
 
     def paths_dev(self, leaf_indices) -> np.ndarray:
         """paths() through the device-side gather (pmx_merkle_ary_paths_dev): node array and indices are uploaded, the paths
@@ -97,7 +153,8 @@ class MerkleTree:
             d_nodes, d_idx, d_out = blocks
             _lib.check(L.pmx_device_upload(dev, d_nodes, ctypes.c_void_p(nodes.ctypes.data), nodes.nbytes, None))
             _lib.check(L.pmx_device_upload(dev, d_idx, ctypes.c_void_p(idx.ctypes.data), idx.nbytes, None))
-            ctx.merkle_ary_paths_dev(d_nodes, self.n_leaves, self.arity, d_idx, idx.shape[0], d_out, None)
+            gather = ctx.merkle_ragged_paths_dev if self.ragged else ctx.merkle_ary_paths_dev
+            gather(d_nodes, self.n_leaves, self.arity, d_idx, idx.shape[0], d_out, None)
             _lib.check(L.pmx_device_download(dev, ctypes.c_void_p(out.ctypes.data), d_out, out.nbytes, None))
             _lib.check(L.pmx_stream_synchronize(dev, None))
         finally:
@@ -107,17 +164,23 @@ class MerkleTree:
 
 
 def verify_paths(parameters: PoseidonConfig, leaves: np.ndarray, indices, paths: np.ndarray, root: np.ndarray,
-                 device: int = 0, arity: int = 2) -> np.ndarray:
+                 device: int = 0, arity: int = 2, n_leaves: int = None) -> np.ndarray:
     """k authentication paths at once: leaves [k][4], indices [k], paths [k][depth][4] -> bool[k]
     (pmx_merkle_verify_paths: one upload, one device step per level, one download; an index with bits at or above
     `depth` names no leaf and verifies as False).  With arity > 2 paths are [k][depth][arity - 1][4]
-    (pmx_merkle_ary_verify_paths; an index >= arity^depth verifies as False)."""
+    (pmx_merkle_ary_verify_paths; an index >= arity^depth verifies as False).
+    n_leaves: the leaf count of a tree over any number of leaves (pmx_merkle_ragged_verify_paths; paths [k][depth][arity - 1][4], or
+    [k][depth][4] at arity 2): the root does not bind it, so the verifier states it, and an index >= n_leaves verifies as False."""
     cur = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
     idx = np.ascontiguousarray(indices, dtype=np.uint64)
     paths = np.ascontiguousarray(paths, dtype=np.uint64)
     k = cur.shape[0]
     root = np.ascontiguousarray(root, dtype=np.uint64).reshape(4)
     ctx = parameters.context(device)
+    if n_leaves is not None:
+        depth, _ = merkle_ragged_shape(n_leaves, arity)
+        assert paths.size == k * depth * (arity - 1) * 4, "paths are [k][depth][arity - 1][4] for the depth of (n_leaves, arity)"
+        return ctx.merkle_ragged_verify_paths(cur, idx, paths, depth, arity, n_leaves, root).astype(bool)
     if arity != 2:
         depth = paths.shape[1] if paths.ndim == 4 else 0
         return ctx.merkle_ary_verify_paths(cur, idx, paths, depth, arity, root).astype(bool)

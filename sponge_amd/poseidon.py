@@ -177,6 +177,14 @@ def merkle_ary_shape(n_leaves: int, arity: int) -> Tuple[int, int]:
     return depth.value, n_nodes.value
 
 
+def merkle_ragged_shape(n_leaves: int, arity: int) -> Tuple[int, int]:
+    """(depth, n_nodes) of the tree of `arity` over any n_leaves >= 1: every level has ceil(width / arity) parents
+    (pmx_merkle_ragged_shape; host only)."""
+    depth, n_nodes = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.lib().pmx_merkle_ragged_shape(n_leaves, arity, ctypes.byref(depth), ctypes.byref(n_nodes)))
+    return depth.value, n_nodes.value
+
+
 def varlen_rows(elems, offsets=None) -> Tuple[np.ndarray, np.ndarray]:
     """(elems [*][4], offsets [n+1]) of variable-length rows, contiguous u64: a list of [L_i][4] arrays (offsets None) is packed."""
     if offsets is None:
@@ -369,6 +377,46 @@ class Context:
         """the same on a device-resident node array, enqueue only; d_work: [k][(arity + 1) * 4] u64 of scratch.  An index >= n_leaves is
         ignored."""
         _lib.check(_lib.lib().pmx_merkle_ary_update_dev(self._h, d_nodes, n_leaves, arity, d_indices, d_new_leaves, k, d_work, stream))
+
+    # ---- trees over any number of leaves (a level's last parent absorbs the children that exist) ---
+    def merkle_ragged(self, leaves: np.ndarray, arity: int, want_nodes: bool = True):
+        """The tree over leaves [n][4], any n >= 1 (pmx_merkle_ragged): (nodes, root), nodes [n_nodes][4] - leaves, then every level,
+        root last - or None.  The root does not bind n."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        depth, n_nodes = merkle_ragged_shape(leaves.shape[0], arity)
+        nodes = np.zeros((n_nodes, 4), dtype=np.uint64) if want_nodes else None
+        root = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_merkle_ragged(self._h, _ptr(leaves), leaves.shape[0], arity, _ptr(nodes), _ptr(root)))
+        return nodes, root
+
+    def merkle_ragged_dev(self, d_nodes: int, n_leaves: int, arity: int, stream: int = 0) -> None:
+        _lib.check(_lib.lib().pmx_merkle_ragged_dev(self._h, d_nodes, n_leaves, arity, stream))
+
+    def merkle_ragged_paths_dev(self, d_nodes: int, n_leaves: int, arity: int, d_indices: int, k: int, d_paths: int, stream: int = 0) -> None:
+        """the opening on the device: d_paths [k][depth][arity - 1][4] from d_nodes; an absent sibling is zeros, and so is the whole path
+        of an index >= n_leaves"""
+        _lib.check(_lib.lib().pmx_merkle_ragged_paths_dev(self._h, d_nodes, n_leaves, arity, d_indices, k, d_paths, stream))
+
+    def merkle_ragged_verify_paths(self, leaves, indices, paths, depth: int, arity: int, n_leaves: int, root) -> np.ndarray:
+        """k authentication paths [k][depth][arity - 1][4] of the tree over n_leaves leaves (pmx_merkle_ragged_verify_paths): uint8[k];
+        an index >= n_leaves verifies as 0."""
+        k = indices.shape[0]
+        ok = np.zeros(k, dtype=np.uint8)
+        _lib.check(_lib.lib().pmx_merkle_ragged_verify_paths(self._h, _ptr(leaves), _ptr(indices), _ptr(paths) if paths.size else None, depth,
+                                                             arity, n_leaves, k, _ptr(root), _ptr(ok)))
+        return ok
+
+    def merkle_ragged_verify_paths_dev(self, d_leaves, d_indices, d_paths, depth: int, arity: int, n_leaves: int, k: int, d_root, d_ok,
+                                       d_work, stream=0) -> None:
+        """d_work: [k][(arity + 1) * 4] u64 of scratch; d_ok: k bytes at any address."""
+        _lib.check(_lib.lib().pmx_merkle_ragged_verify_paths_dev(self._h, d_leaves, d_indices, d_paths, depth, arity, n_leaves, k, d_root,
+                                                                 d_ok, d_work, stream))
+
+    def merkle_ragged_update_dev(self, d_nodes: int, n_leaves: int, arity: int, d_indices: int, d_new_leaves: int, k: int, d_work: int,
+                                 stream: int = 0) -> None:
+        """leaf updates of a device-resident node array of the ragged layout, enqueue only; d_work: [k][(arity + 1) * 4] u64 of scratch.
+        An index >= n_leaves is ignored."""
+        _lib.check(_lib.lib().pmx_merkle_ragged_update_dev(self._h, d_nodes, n_leaves, arity, d_indices, d_new_leaves, k, d_work, stream))
 
     # ---- device-pointer entry points (only enqueue; pointers are raw device addresses) ---------
     def permute_batch_dev(self, d_states: int, n: int, stream: int = 0) -> None:
