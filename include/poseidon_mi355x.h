@@ -28,6 +28,14 @@
  * concurrently (the absorb / squeeze ones take a short lock inside the context while they enqueue).  Distinct contexts are independent.  Every call runs with its context's device current and restores
  * the calling thread's current HIP device before it returns; a `stream` argument must belong to the context's device.
  *
+ * Graph capture (*_dev entry points): each entry below says whether it may be captured into a hipGraph.  Those that may only launch
+ * kernels and device-to-device copies on the caller's stream: they allocate nothing, synchronise nothing, ask the stream nothing and keep
+ * no host copy of the data, so a captured call records all its work and nothing else, executes nothing while it is captured, needs no
+ * earlier call to warm anything up (the captured launch may be the first launch of its kernel in the process) and on replay works on
+ * whatever the buffers then hold (tests/test_gpu_streams.py).  The pass-form drivers, the variable-length entries and squeeze bytes /
+ * bits must NOT be captured: their scratch comes from a per-stream pool of the context that may call hipMalloc.  The pmx_mgpu_*_dev
+ * entries enqueue on the group's own streams and are not meant for capture.
+ *
  * Alignment of device pointers (*_dev entry points): every array of field elements - states, messages, digests, nodes, leaves,
  * paths, the root, d_work - must be 16-byte aligned (PMX_ERR_ARG "device pointers must be 16-byte aligned" otherwise, nothing
  * launched).  Every other array needs the natural alignment of its element type and no more: mode words (d_mode_tag, d_mode_index:
@@ -173,14 +181,15 @@ int pmx_ctx_engine_info(const pmx_ctx *ctx, int op, size_t n, size_t len, pmx_en
  * PoseidonSponge::permute (src/poseidon/mod.rs:95-118 with apply_ark :76-80, apply_s_box :63-74,
  * apply_mds :82-93) applied independently to n states, in place.  states: [n][t][4].
  * The host variant copies in, runs the kernel, copies out.  The _dev variant takes a device pointer
- * and a hipStream_t (NULL = default stream) and only enqueues.  */
+ * and a hipStream_t (NULL = default stream) and only enqueues: one launch, nothing allocated; it may be captured into a graph.  */
 int pmx_permute_batch(pmx_ctx *ctx, uint64_t *states, size_t n);
 int pmx_permute_batch_dev(pmx_ctx *ctx, uint64_t *d_states, size_t n, void *stream);
 
 /* ---- fixed-shape hash driver ------------------------------------------------------------------
  * Per row: PoseidonSponge::new; absorb(in_len native elements); squeeze_native_field_elements(out_len)
  * (src/poseidon/mod.rs:219-254, 321-341).  in: [n][in_len][4], out: [n][out_len][4].  in_len may be 0
- * (absorb of an empty input is a no-op, mod.rs:234-236). */
+ * (absorb of an empty input is a no-op, mod.rs:234-236).  The _dev variant is one launch on the caller's stream, nothing allocated; it may
+ * be captured into a graph. */
 int pmx_hash_batch(pmx_ctx *ctx, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, size_t n);
 int pmx_hash_batch_dev(pmx_ctx *ctx, const uint64_t *d_in, size_t in_len, uint64_t *d_out, size_t out_len,
                        size_t n, void *stream);
@@ -278,7 +287,8 @@ int pmx_sponge_squeeze_bits_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t
  * leaves: [n_leaves][4], n_leaves a power of two.  nodes (may be NULL): [2*n_leaves-1][4] receives the
  * leaves, then every level, root last.  root (may be NULL): [4]. */
 int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint64_t *nodes, uint64_t *root);
-/* Device variant: d_nodes [2*n_leaves-1][4] must already hold the leaves in its first n_leaves rows. */
+/* Device variant: d_nodes [2*n_leaves-1][4] must already hold the leaves in its first n_leaves rows.  One launch per level on the caller's
+ * stream, nothing allocated; it may be captured into a graph. */
 int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream);
 
 /* n_trees independent 2-to-1 trees of leaves_per_tree leaves each (a power of two; n_trees is any number >= 1), advanced
@@ -287,7 +297,8 @@ int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *
  * leaves: [n_trees][leaves_per_tree][4] (tree after tree); nodes (may be NULL): [n_trees * (2*leaves_per_tree - 1)][4] receives
  * the leaves, then level 1 of every tree (tree after tree), ..., then the n_trees roots; roots (may be NULL): [n_trees][4].
  * Tree b's node j of level l (level 0 = leaves, m = leaves_per_tree) is row  n_trees*(2m - 2m/2^l) + b*(m/2^l) + j.
- * The device variant takes d_nodes with the leaves in its first n_trees*leaves_per_tree rows and only enqueues.
+ * The device variant takes d_nodes with the leaves in its first n_trees*leaves_per_tree rows and only enqueues (one launch per level,
+ * nothing allocated; it may be captured into a graph).
  * (No counterpart in the reference: a parent is new; absorb([l, r]); squeeze_native(1) as above.) */
 int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint64_t *nodes,
                            uint64_t *roots);
@@ -301,7 +312,8 @@ int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, 
  * pmx_merkle_verify_paths: k paths at once - one upload, `depth` level steps on the device (each a batched 2-to-1
  * compression of all k running nodes), one download: ok_out[i] = 1 iff hashing leaves[i] up its path (indices[i] says
  * left / right at each level) gives `root` and indices[i] < 2^depth.
- * pmx_merkle_verify_paths_dev: the same on device-resident buffers, enqueue only; d_work is [k][12] u64 of scratch.  d_leaves, d_paths,
+ * pmx_merkle_verify_paths_dev: the same on device-resident buffers, enqueue only (a device-to-device copy, two launches per level, one for
+ * the verdicts; nothing allocated: it may be captured into a graph); d_work is [k][12] u64 of scratch.  d_leaves, d_paths,
  * d_root and d_work are 16-byte aligned like every array of elements; d_indices needs 8 bytes, d_ok (k single bytes) any address. */
 int pmx_merkle_paths(const uint64_t *nodes, size_t n_leaves, const uint64_t *indices, size_t k, uint64_t *paths_out);
 int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
@@ -322,6 +334,8 @@ int pmx_merkle_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const ui
  *   that is no power of the arity, a node array whose byte size overflows size_t (PMX_ERR_ARG).
  * nodes: [n_nodes][4], the leaves, then every level, root last; the _dev variants take d_nodes with the leaves in its first rows
  *   and only enqueue.  nodes / root / roots may be NULL in the host entries.
+ * Capture: every _dev entry of this family (pmx_merkle_ary_dev, _forest_dev, _paths_dev, _verify_paths_dev) launches on the caller's stream
+ *   only and allocates nothing; each may be captured into a graph.
  * Forest, level-major like pmx_merkle_2to1_forest: level l of every tree, tree after tree.  With m = leaves_per_tree, tree b's node j
  *   of level l is row  n_trees * (m + m/arity + ... + m/arity^(l-1)) + b * (m / arity^l) + j;  the last n_trees rows are the roots.
  * Paths: [k][depth][arity - 1][4], bottom-up; per level the siblings in child order with the running node's own slot left out (the
@@ -409,11 +423,13 @@ int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_leaves, uint32
  *   included; the short last row is bounded inside that launch and nothing at or beyond the level's end is read.
  * Paths: [k][depth][arity - 1][4] as for pmx_merkle_ary_paths; a sibling that does not exist (its index is at or beyond its level's
  *   width) is four zero words.  pmx_merkle_ragged_paths: host-only gather, an index >= n_leaves is PMX_ERR_ARG and nothing is written.
- *   pmx_merkle_ragged_paths_dev: the gather on the device, enqueue only; an index >= n_leaves gets an all-zero path.
+ *   pmx_merkle_ragged_paths_dev: the gather on the device, enqueue only (one launch, nothing allocated; it may be captured into a graph);
+ *   an index >= n_leaves gets an all-zero path.
  * Verification: ok[i] = 1 iff hashing leaves[i] up its path gives `root` AND indices[i] < n_leaves.  The climb is that of
  *   pmx_merkle_ary_verify_paths* (absent siblings are zeros, so every row is a full one); d_work is [k][(arity + 1) * 4] u64.  depth must
- *   be the depth of (n_leaves, arity): PMX_ERR_ARG otherwise.
- * pmx_merkle_ragged_update_dev: the contract of pmx_merkle_ary_update_dev - enqueue only, nothing allocated, the same d_work, indices
+ *   be the depth of (n_leaves, arity): PMX_ERR_ARG otherwise.  pmx_merkle_ragged_verify_paths_dev only enqueues and allocates nothing; it may
+ *   be captured into a graph.
+ * pmx_merkle_ragged_update_dev: the contract of pmx_merkle_ary_update_dev - enqueue only, nothing allocated (it may be captured), the same d_work, indices
  *   >= n_leaves ignored, whole-level launches from the first level with k >= W parents on; afterwards the array is byte for byte what a
  *   rebuild over the new leaves gives.  (There is no host-array pmx_merkle_ragged_update, no ragged forest and no device-group form.)
  * Errors, nothing launched or written on any: PMX_ERR_ARG for arity < 2, n_leaves = 0, byte sizes that overflow, a depth that is not the
@@ -492,7 +508,8 @@ int pmx_mgpu_hash_batch(pmx_mgpu *g, const uint64_t *in, size_t in_len, uint64_t
  * pmx_shard_bounds(n_total, world, first_rank + local).  Only enqueues. */
 int pmx_mgpu_permute_shards_dev(pmx_mgpu *g, uint64_t *const *d_shards, size_t n_total);
 /* The final gather: d_all[local] = [n_total][row_elems][4] on every device receives all shards in rank order
- * (row_elems = t for states, 1 for digests).  RCCL; only enqueues. */
+ * (row_elems = t for states, 1 for digests).  RCCL; only enqueues.  (None of the pmx_mgpu_*_dev entries takes a stream: they run on the
+ * group's own streams and are not meant for graph capture.) */
 int pmx_mgpu_all_gather_dev(pmx_mgpu *g, const uint64_t *const *d_shards, uint64_t *const *d_all, size_t n_total,
                             size_t row_elems);
 /* The gather to ONE rank: only `root` ends with all shards (d_all of its slot; the other slots' entries are not read and may be

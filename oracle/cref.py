@@ -167,6 +167,43 @@ class CRef:
                                   ctypes.byref(i), self._ptr(out), ctypes.c_size_t(n))
         return state, m.value, i.value, out
 
+    def _each_sponge(self, states, tags, indices, call):
+        """call(i, state*, mode*, index*) for every sponge of copies of the three arrays, which the C port updates in place; a few
+        threads share the sponges (ctypes releases the GIL).  Returns the copies."""
+        from concurrent.futures import ThreadPoolExecutor
+        states = np.ascontiguousarray(states, dtype=np.uint64).copy()
+        tags, indices = np.ascontiguousarray(tags, dtype=np.uint32).copy(), np.ascontiguousarray(indices, dtype=np.uint32).copy()
+        n, row = tags.shape[0], self.cfg.t * 32
+        s0, m0, i0 = states.ctypes.data, tags.ctypes.data, indices.ctypes.data
+
+        def some(first):
+            for i in range(first, min(first + 1024, n)):
+                call(i, ctypes.c_void_p(s0 + i * row), ctypes.c_void_p(m0 + 4 * i), ctypes.c_void_p(i0 + 4 * i))
+        with ThreadPoolExecutor(min(8, max_threads())) as pool:
+            list(pool.map(some, range(0, n, 1024)))
+        return states, tags, indices
+
+    def sponge_absorb_each(self, states, tags, indices, elems, offsets):
+        """sponge_absorb on n sponges: sponge i absorbs elems[offsets[i] : offsets[i + 1]]; a sponge whose row is empty is left untouched
+        (mod.rs:234-236).  states [n][t][4], tags / indices [n] u32.  Returns (states, tags, indices)."""
+        elems = np.ascontiguousarray(elems, dtype=np.uint64).reshape(-1, 4)
+        off = [int(x) for x in offsets]
+        cfg, fn, base = ctypes.byref(self._c), lib().pref_sponge_absorb, elems.ctypes.data
+
+        def call(i, state, mode, index):
+            if off[i + 1] > off[i]:
+                fn(cfg, state, mode, index, ctypes.c_void_p(base + 32 * off[i]), ctypes.c_size_t(off[i + 1] - off[i]))
+        return self._each_sponge(states, tags, indices, call)
+
+    def sponge_squeeze_each(self, states, tags, indices, n_out):
+        """sponge_squeeze of n_out elements on n sponges.  Returns (states, tags, indices, out [n][n_out][4])."""
+        out = np.zeros((len(tags), n_out, 4), dtype=np.uint64)
+        cfg, fn, base = ctypes.byref(self._c), lib().pref_sponge_squeeze, out.ctypes.data
+
+        def call(i, state, mode, index):
+            fn(cfg, state, mode, index, ctypes.c_void_p(base + 32 * n_out * i), ctypes.c_size_t(n_out))
+        return self._each_sponge(states, tags, indices, call) + (out,)
+
 
 def usable_cpus():
     """CPUs this process may actually use: affinity mask capped by the cgroup CPU quota (cpu.max), if any."""

@@ -84,3 +84,26 @@ def test_c_random_batch_vs_python_and_thread_invariance():
     assert np.array_equal(a, b)
     want = [x for i in range(64) for x in O.permute(cfg, vals[3 * i:3 * i + 3])]
     assert cref.limbs_to_elems(a, cfg.p) == want
+
+
+def test_c_sponge_calls_on_a_batch_equal_the_calls_on_one_sponge():
+    """CRef.sponge_absorb_each / sponge_squeeze_each (the C port walked over n sponges through pointers, several threads) against
+    CRef.sponge_absorb / sponge_squeeze sponge by sponge: every mode, rows of length 0 .. 3 rate + 1, more sponges than one thread's share"""
+    cfg = oracle_config("bls_t3_a5_8_31")
+    cr = cref.CRef(cfg)
+    rng = random.Random(11)
+    n, t, r = 2100, cfg.t, cfg.rate
+    states = cref.elems_to_limbs([rng.randrange(cfg.p) for _ in range(n * t)], cfg.p).reshape(n, t, 4)
+    tags = np.array([i % 2 for i in range(n)], dtype=np.uint32)
+    idx = np.array([rng.randrange(r + 1) for _ in range(n)], dtype=np.uint32)
+    lens = [i % (3 * r + 2) for i in range(n)]
+    offsets = np.concatenate([[5], 5 + np.cumsum(lens)]).astype(np.uint64)
+    elems = cref.elems_to_limbs([rng.randrange(cfg.p) for _ in range(int(offsets[-1]))], cfg.p)
+    got = cr.sponge_absorb_each(states, tags, idx, elems, offsets)
+    sq = cr.sponge_squeeze_each(states, tags, idx, 2 * r + 1)
+    for i in list(range(40)) + list(range(n - 40, n)) + [1023, 1024, 1025]:
+        row = elems[int(offsets[i]):int(offsets[i + 1])]
+        want = cr.sponge_absorb(states[i], int(tags[i]), int(idx[i]), row) if lens[i] else (states[i], tags[i], idx[i])
+        assert np.array_equal(got[0][i], want[0]) and (got[1][i], got[2][i]) == (want[1], want[2]), i
+        want = cr.sponge_squeeze(states[i], int(tags[i]), int(idx[i]), 2 * r + 1)
+        assert np.array_equal(sq[0][i], want[0]) and (sq[1][i], sq[2][i]) == (want[1], want[2]) and np.array_equal(sq[3][i], want[3]), i
