@@ -49,6 +49,7 @@ pub const PMX_OP_HASH: c_int = 1;
 pub const PMX_OP_COMPRESS: c_int = 2;
 pub const PMX_OP_ABSORB: c_int = 3;
 pub const PMX_OP_SQUEEZE: c_int = 4;
+pub const PMX_OP_GRIND: c_int = 5;
 
 pub const PMX_MODE_ABSORBING: u32 = 0;
 pub const PMX_MODE_SQUEEZING: u32 = 1;
@@ -92,6 +93,9 @@ extern "C" {
                                          out: *mut u8, num_bits: usize, n: usize) -> c_int;
     pub fn pmx_sponge_squeeze_bits_batch_dev(ctx: *mut pmx_ctx, d_states: *mut u64, d_mode_tag: *mut u32, d_mode_index: *mut u32,
                                              d_out: *mut u8, num_bits: usize, n: usize, stream: *mut c_void) -> c_int;
+    // proof-of-work grinding: the smallest nonce of [first, first + count) whose absorption makes the sponge squeeze `bits` zero bits
+    pub fn pmx_sponge_grind(ctx: *mut pmx_ctx, state: *const u64, mode_tag: u32, mode_index: u32, bits: u32, first: u64, count: u64,
+                            nonce_out: *mut u64, found_out: *mut c_int) -> c_int;
     // variable-length rows: row i is input[offsets[i] .. offsets[i + 1]), offsets [n + 1]
     pub fn pmx_hash_varlen_batch(ctx: *mut pmx_ctx, input: *const u64, offsets: *const u64, out: *mut u64, out_len: usize,
                                  n: usize) -> c_int;

@@ -73,6 +73,24 @@ impl<F: PrimeField> Mi355xPoseidonSponge<F> {
             DuplexSpongeMode::Squeezing { next_squeeze_index: index as usize }
         };
     }
+
+    /// Proof-of-work grinding (`pmx_sponge_grind`; no counterpart in the reference): the smallest nonce `v` of
+    /// `[first, first + count)` such that `c = self.clone(); c.absorb(&F::from(v)); c.squeeze_bits(bits)` is all false, or `None`.
+    /// `bits < F::MODULUS_BIT_SIZE`.  About 2^bits permutations of this one state, fused on the device; the sponge is not modified:
+    /// `self.absorb(&F::from(v))` with the winner goes on with the transcript.
+    pub fn grind(&self, bits: u32, first: u64, count: u64) -> Option<u64> {
+        let (tag, idx) = self.mode_words();
+        let (mut nonce, mut found) = (0u64, 0);
+        check(unsafe { ffi::pmx_sponge_grind(self.ctx.0, limbs(&self.state), tag, idx, bits, first, count, &mut nonce, &mut found) });
+        if found != 0 { Some(nonce) } else { None }
+    }
+
+    /// The acceptance rule itself on a clone, through the trait's own absorb and squeeze_bits (what a verifier runs).
+    pub fn check_pow(&self, nonce: u64, bits: usize) -> bool {
+        let mut c = self.clone();
+        c.absorb(&F::from(nonce));
+        c.squeeze_bits(bits).iter().all(|b| !*b)
+    }
 }
 
 impl<F: PrimeField> CryptographicSponge for Mi355xPoseidonSponge<F> {

@@ -160,6 +160,7 @@ int pmx_ctx_width(const pmx_ctx *ctx);
 #define PMX_OP_COMPRESS 2
 #define PMX_OP_ABSORB 3
 #define PMX_OP_SQUEEZE 4
+#define PMX_OP_GRIND 5     /* one chunk of n candidates of pmx_sponge_grind */
 typedef struct pmx_engine_info {
     char engine[64];     /* e.g. "QuadEngine<5>", "HybridEngine<9,5,mfma,windows of 9>", "... x passes", "LdsEngine<5>" */
     int width;           /* t */
@@ -281,6 +282,36 @@ int pmx_sponge_squeeze_bits_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode
                                   size_t num_bits, size_t n);
 int pmx_sponge_squeeze_bits_batch_dev(pmx_ctx *ctx, uint64_t *d_states, uint32_t *d_mode_tag, uint32_t *d_mode_index, uint8_t *d_out,
                                       size_t num_bits, size_t n, void *stream);
+
+/* ---- proof-of-work grinding ------------------------------------------------------------------------
+ * The grinding step of a FRI / STARK transcript: find a nonce whose absorption makes the transcript squeeze `bits` zero bits.  About 2^bits
+ * independent permutations of ONE sponge state; the candidates exist only in registers.  (No counterpart in the reference; the acceptance
+ * rule is defined through its absorb and squeeze_bits, src/poseidon/mod.rs:232-254, 272-286.)
+ * Inputs: a sponge (state [t][4], mode_tag, mode_index) of the context's config, a difficulty `bits`, a nonce range [first, first + count).
+ * A nonce v (a uint64_t) is ACCEPTED iff
+ *     c = sponge.clone(); c.absorb(&F::from(v)); c.squeeze_bits(bits) is all false.
+ * With B the bit length of the modulus and bits <= B - 1 that is: the low `bits` bits of the canonical integer of the first squeezed
+ * element are zero.  In permutations:
+ *   Absorbing{i}, i < rate:           add the ABI residue of v (v * 2^256 mod p, what F::from(v) holds) into state[capacity + i], permute
+ *                                     once, test state[capacity].
+ *   Absorbing{rate} or Squeezing{any}: the reference permutes before it absorbs (mod.rs:239-252).  That permutation does not depend on v:
+ *                                     it is done ONCE for the whole search, and the rule is then the case above with i = 0.
+ * Result: *found_out = 1 and *nonce_out = the SMALLEST accepted nonce of the range, or *found_out = 0 (*nonce_out is then not written).
+ *   Deterministic whatever the launch geometry.  The caller's sponge is not modified: the caller absorbs the winning nonce with the
+ *   entries above (pmx_sponge_absorb_batch with n = 1 and the element F::from(nonce)).
+ * Host-buffer entry only: one state goes up and one word comes down, so device residency buys nothing.  It serialises on the context's
+ *   host lock like every host-buffer entry and runs inside the catch-all.  The range is searched in chunks of 2^21 candidates (measured:
+ *   profiles/grind/README.md), in ascending order, one launch each; the search stops behind the first chunk that reports a hit.
+ * Errors (PMX_ERR_ARG, nothing launched): a null pointer; a mode word the host drivers refuse (a tag that is neither mode, an index above the
+ *   rate); bits > B - 1 (a second squeezed element would be needed); first + count > 2^64.
+ * count = 0: PMX_OK, *found_out = 0, nothing launched.  bits = 0: every nonce is accepted - *nonce_out = first, nothing launched.
+ * Engine: pmx_ctx_engine_info(ctx, PMX_OP_GRIND, n, 0) names the engine of a chunk of n candidates; the choice is that of a 2-to-1
+ *   compression of n parents (the quad engine for the split (rate 2, capacity 1) of t = 3 up to 32768 candidates, the window engines for
+ *   t = 3 .. 9, the run-time-width engine otherwise).
+ * What this family lacks: there is no *_dev entry - a capturable form on device-resident state and result words comes later, together with
+ *   its stream and capture tests -, no batch of sponges in one call and no device-group form. */
+int pmx_sponge_grind(pmx_ctx *ctx, const uint64_t *state /*[t][4], host*/, uint32_t mode_tag, uint32_t mode_index,
+                     uint32_t bits, uint64_t first, uint64_t count, uint64_t *nonce_out, int *found_out);
 
 /* ---- 2-to-1 Merkle compression ------------------------------------------------------------------
  * parent = (new; absorb([left, right]); squeeze_native(1))[0]  (needs rate >= 2), level by level.

@@ -1,9 +1,9 @@
 /*
- * poseidon_mi355x_testing.h -- test hooks of the device-group code.  NOT part of the product ABI (poseidon_mi355x.h),
+ * poseidon_mi355x_testing.h -- test hooks: of the device-group code (pmx_mgpu.cpp) and of the grinding search's chunk size (pmx_hooks.cpp).  NOT part of the product ABI (poseidon_mi355x.h),
  * not in the Rust binding; the reference has no counterpart (it has no multi-device code at all,
  * src/poseidon/mod.rs:62-183).
  *
- * These symbols exist ONLY in libposeidon_mi355x_test.so: the shipped objects with pmx_mgpu.cpp compiled -DPMX_TEST_HOOKS
+ * These symbols exist ONLY in libposeidon_mi355x_test.so: the shipped objects with pmx_mgpu.cpp and pmx_hooks.cpp compiled -DPMX_TEST_HOOKS
  * (sponge_amd/csrc/Makefile).  libposeidon_mi355x.so, the library that ships, neither exports them nor contains the state
  * they set (tests/test_abi_and_host.py checks both export tables).  State is process-wide and atomic.  The test build also
  * reads PMX_RCCL_LIBRARY=<path> when the first group is formed and binds THAT collective library (the tests' stand-in,
@@ -29,6 +29,11 @@ int pmx_mgpu_test_fault(int fail_local, int no_threads);
  * device, so this is only useful behind the stand-in collective library of tests/fake_rccl/, which lets every
  * world > 1 branch of the device-group code run on a one-GPU box. */
 int pmx_mgpu_test_shared_device(int allow);
+
+/* pmx_sponge_grind walks its nonce range in chunks of `candidates` per launch instead of the product's measured chunk (0: the product's
+ * again).  For the test that needs a first hit in the THIRD chunk with an oracle leg of a few thousand permutations, and for the chunk
+ * sweep of tools/grind_rate.py, which takes every size through the product's own host loop. */
+int pmx_test_grind_chunk(uint64_t candidates);
 
 #ifdef __cplusplus
 }

@@ -54,7 +54,7 @@ class PmxMgpuInfo(ctypes.Structure):
     ]
 
 
-OP_PERMUTE, OP_HASH, OP_COMPRESS, OP_ABSORB, OP_SQUEEZE = range(5)
+OP_PERMUTE, OP_HASH, OP_COMPRESS, OP_ABSORB, OP_SQUEEZE, OP_GRIND = range(6)
 
 
 class PmxEngineInfo(ctypes.Structure):
@@ -125,6 +125,8 @@ SIGNATURES = {
     "pmx_sponge_squeeze_bits_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, ctypes.c_void_p, _sz, _sz]),
     "pmx_sponge_squeeze_bits_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, ctypes.c_void_p, _sz, _sz,
                                                          ctypes.c_void_p]),
+    "pmx_sponge_grind": (ctypes.c_int, [ctypes.c_void_p, _u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                        ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
     "pmx_hash_varlen_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, _sz]),
     "pmx_hash_varlen_batch_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _sz, _u64p, _sz, _sz, ctypes.c_void_p]),
     "pmx_sponge_absorb_varlen_batch": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u32p, _u32p, _u64p, _u64p, _sz]),
@@ -197,6 +199,7 @@ TEST_HOOK_SIGNATURES = {
     "pmx_test_hooks_enabled": (ctypes.c_int, []),
     "pmx_mgpu_test_fault": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "pmx_mgpu_test_shared_device": (ctypes.c_int, [ctypes.c_int]),
+    "pmx_test_grind_chunk": (ctypes.c_int, [ctypes.c_uint64]),
 }
 
 _lib = None

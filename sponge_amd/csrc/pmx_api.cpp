@@ -19,6 +19,7 @@
 #include "pmx_internal.hpp"
 #include "pmx_prepare.hpp"
 #include "pmx_launch.hpp"
+#include "pmx_grind_plan.hpp"
 #include "pmx_merkle_plan.hpp"
 #include "pmx_sponge_plan.hpp"
 #include "pmx_squeeze_cut.hpp"
@@ -874,6 +875,65 @@ extern "C" int pmx_sponge_squeeze_bytes_batch(pmx_ctx *ctx, uint64_t *states, ui
 extern "C" int pmx_sponge_squeeze_bits_batch(pmx_ctx *ctx, uint64_t *states, uint32_t *mode_tag, uint32_t *mode_index, uint8_t *out,
                                              size_t num_bits, size_t n) {
     return squeeze_cut_host(ctx, states, mode_tag, mode_index, out, num_bits, n, true, "pmx_sponge_squeeze_bits_batch");
+}
+
+// ---- proof-of-work grinding ------------------------------------------------------------------------
+// The smallest nonce v of [first, first + count) with  c = sponge.clone(); c.absorb(&F::from(v)); c.squeeze_bits(bits) all false
+// (mod.rs:232-254, 272-286): one state up, one word down, the candidates exist only in registers (pmx_device.hip: grind_kernel).
+// An Absorbing{rate} or Squeezing sponge permutes before it absorbs (mod.rs:239-252) whatever the nonce: that permutation runs once,
+// on the copy of the state in the context's staging memory, and the search then absorbs at index 0.  The range is walked in chunks
+// (pmx_grind_plan.hpp) of grind_chunk() candidates, the result words read back behind each.
+extern "C" int pmx_sponge_grind(pmx_ctx *ctx, const uint64_t *state, uint32_t mode_tag, uint32_t mode_index, uint32_t bits, uint64_t first,
+                                uint64_t count, uint64_t *nonce_out, int *found_out) {
+    PMX_ABI_BEGIN("pmx_sponge_grind")
+    if (!ctx || !state || !nonce_out || !found_out) return set_error(PMX_ERR_ARG, "pmx_sponge_grind: null pointer");
+    int rc = check_modes(ctx, &mode_tag, &mode_index, 1);
+    if (rc) return rc;
+    const uint32_t modulus_bit_size = modulus_bits(ctx->dev.field);
+    if (bits > modulus_bit_size - 1)
+        return set_error(PMX_ERR_ARG, "pmx_sponge_grind: %u bits is more than one squeezed element yields (%u)", bits, modulus_bit_size - 1);
+    if (!grind_range_ok(first, count)) return set_error(PMX_ERR_ARG, "pmx_sponge_grind: the nonce range ends beyond 2^64");
+    *found_out = 0;
+    if (count == 0) return PMX_OK;
+    if (bits == 0) {   // squeeze_bits(0) is empty: every nonce is accepted
+        *nonce_out = first;
+        *found_out = 1;
+        return PMX_OK;
+    }
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    // staging: [state t x 32 bytes | the smallest accepted nonce | whether there is one], one copy up, 16 bytes down per chunk
+    const size_t st_bytes = (size_t)ctx->t * 32;
+    if (!ctx->pinned) PMX_HIP(hipHostMalloc(&ctx->pinned, kSmallCallBytes, hipHostMallocDefault));
+    void *d = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, st_bytes + 16, &d))) return rc;
+    char *h = (char *)ctx->pinned;
+    uint64_t *h_res = (uint64_t *)(h + st_bytes), *d_state = (uint64_t *)d, *d_res = (uint64_t *)((char *)d + st_bytes);
+    std::memcpy(h, state, st_bytes);
+    h_res[0] = UINT64_MAX;
+    h_res[1] = 0;
+    StreamDrain drain{ctx};
+    hipStream_t st = ctx->stream;
+    PMX_HIP(hipMemcpyAsync(d, h, st_bytes + 16, hipMemcpyHostToDevice, st));
+    uint32_t index = mode_index;
+    if (mode_tag == PMX_MODE_SQUEEZING || index == ctx->dev.rounds.rate) {   // mod.rs:241-244, 250: the same for every nonce
+        PMX_HIP(launch_permute(ctx->dev, ctx->t, d_state, 1, st));
+        index = 0;
+    }
+    const uint64_t chunk = grind_chunk(), chunks = grind_chunks(count, chunk);
+    for (uint64_t k = 0; k < chunks; ++k) {
+        const GrindChunk c = grind_chunk_at(first, count, chunk, k);
+        PMX_HIP(launch_grind(ctx->dev, ctx->t, d_state, index, bits, c.first, (size_t)c.count, d_res, st));
+        PMX_HIP(hipMemcpyAsync(h_res, d_res, 16, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipStreamSynchronize(st));
+        if (h_res[1]) {
+            *nonce_out = h_res[0];
+            *found_out = 1;
+            break;
+        }
+    }
+    return PMX_OK;
+    PMX_ABI_END
 }
 
 // ---- variable-length rows ------------------------------------------------------------------------

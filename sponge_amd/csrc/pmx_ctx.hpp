@@ -70,6 +70,12 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
+// Candidates per launch of pmx_sponge_grind (pmx_api.cpp).  Defined in pmx_hooks.cpp, the object that exists in a shipped and a test
+// build: the measured constant in the shipped library; the test build lets pmx_test_grind_chunk (include/poseidon_mi355x_testing.h)
+// replace it, so that a test can put a hit into the third chunk without an oracle leg of two product chunks, and the chunk sweep can
+// take every size through the product's own host loop.
+uint64_t grind_chunk();
+
 #define PMX_BIND(ctx)                                                                \
     ::pmx::DeviceGuard device_guard_((ctx)->device);                                 \
     if (device_guard_.err != hipSuccess) return ::pmx::hip_fail(device_guard_.err, "hipSetDevice")

@@ -809,6 +809,57 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     if (active && e.owns(e.c.capacity)) abi_store(reinterpret_cast<uint32_t *>(out + gid * 4), digest);
 }
 
+// Proof-of-work grinding on ONE sponge (pmx_sponge_grind; include/poseidon_mi355x.h has the contract): unit gid tries the nonce
+// v = first + gid, i.e. the state  base; state[capacity + index] += F::from(v); permute  (mod.rs:232-254 at Absorbing{index}, index <
+// rate - the launcher has already performed the permutation the other modes start with), and accepts v when the low `bits` bits of the
+// canonical integer of state[capacity] - the first element a squeeze would hand out, mod.rs:272-286 - are zero.  best[0] starts at
+// UINT64_MAX and ends as the smallest accepted nonce of the launch; best[1] starts at 0 and ends as 1 if there is one.
+// No per-candidate memory: `base` is one row of t ABI elements at a wave-uniform address (scalar loads, 32 t bytes for everybody),
+// each loaded by the lane that holds it; the nonce's residue costs one Montgomery product (abi_from_u64) in front of the permutation
+// on the quad and window engines, whose from_abi is a bit-slice - two on the run-time-width engine, whose from_abi is an exact
+// conversion of its own (against the t^2 products per round of its dense schedule) -,
+// and only the digest lane of the last layer is computed, as in compress_kernel.  One atomic per wave at most, in the shape of
+// sponge_queue: lanes are in nonce order, so the lowest accepting lane of the ballot holds the wave's smallest nonce.
+// A workgroup whose first nonce lies above a nonce already found leaves before it permutes - nothing it could find would lower the
+// minimum, so the result stays exact whatever the launch geometry and the order the workgroups run in.  `best` is written by other
+// workgroups of this very launch: it is read with a device-scope atomic load, past the scalar cache and the vector L1, like the
+// lists of permute_listed_kernel.  (The exit is taken behind the engine's construction - QuadEngine stages its table behind a
+// barrier - and no engine's permutation holds a workgroup barrier.)
+template <class Engine>
+__global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
+    grind_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ base, uint32_t index, uint32_t bits,
+                 uint64_t first, size_t n, uint64_t *__restrict__ best) {
+    Engine e(d, consts);
+    // (one value per wave - the first lane's - so the exit is wave-uniform by construction and a scalar branch: no lane reaches the
+    // lane-pair exchange of permute_hybrid or the quad moves with its partner gone.  Waves of one workgroup may see different values
+    // and decide differently; the answer is exact either way, because any value seen is a nonce some wave has accepted.)
+    const uint64_t seen = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t found = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)seen) |
+                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(seen >> 32)) << 32);
+    if (found < first + (uint64_t)blockIdx.x * Engine::kUnits) return;   // (blockIdx.x * kUnits < n: the sum does not wrap)
+    const size_t gid = Engine::unit();
+    const bool active = gid < n;
+    const uint64_t nonce = first + gid;
+    const uint32_t t_all = e.c.rate + e.c.capacity, at = e.c.capacity + index;
+    const uint32_t *row = reinterpret_cast<const uint32_t *>(base);
+    e.zero();
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < t_all; ++i) {
+        if (e.owns(i)) e.set(i, e.from_abi(abi_load(row + 8 * i)));
+    }
+    // state[capacity + index] += F::from(nonce) (mod.rs:128), normalised like every absorbed element (absorb_elements)
+    const Fe x = e.from_abi(abi_from_u64(nonce, e.f));
+    if (e.owns(at)) e.set(at, fe_normalize(fe_add_lazy(e.get(at), x)));
+    e.permute(e.c.capacity, e.c.capacity + 1);   // only the digest lane of the result is read
+    const Abi digest = abi_to_canonical(e.to_abi(e.get(e.c.capacity)), e.f);
+    const bool hit = active && e.owns(e.c.capacity) && canonical_low_bits_zero(digest, bits);
+    const uint64_t hits = __builtin_amdgcn_ballot_w64(hit);
+    if (hits && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(hits)) {
+        atomicMin(reinterpret_cast<unsigned long long *>(best), (unsigned long long)nonce);
+        best[1] = 1;   // (every writer writes the same value; the nonce 2^64 - 1 is a nonce like any other, not "none")
+    }
+}
+
 // (per-lane engines: every lane keeps its own cursor and length - lanes of a wave may absorb rows of different lengths; a lane whose
 // row is empty absorbs nothing and leaves its mode words alone, mod.rs:234-236)
 template <class Engine, class Rows>
@@ -1065,6 +1116,13 @@ struct Launch {
                            c.consts, in, arity, n_children, out, n);
         return hipGetLastError();
     }
+    static hipError_t grind(const DevConfig &c, uint32_t t, const uint64_t *base, uint32_t index, uint32_t bits, uint64_t first, size_t n,
+                            uint64_t *best, hipStream_t st) {
+        allow_lds(grind_kernel<Engine>, Engine::lds_bytes(c, t));
+        hipLaunchKernelGGL(grind_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                           c.consts, base, index, bits, first, n, best);
+        return hipGetLastError();
+    }
     // absorb / squeeze: per-lane kernels, or - on an engine whose permutation must stay wave-uniform - passes on its permutation
     // (pmx_sponge_plan.hpp).  Only the form the engine has is instantiated.
     template <class Rows>
@@ -1159,7 +1217,7 @@ struct Launch {
 template <class Engine>
 static const EngineOps &engine_ops() {
     using L = Launch<Engine>;
-    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::compress_ary, &L::compress_ary_bounded, &L::absorb, &L::absorb_varlen, &L::squeeze,
+    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::compress_ary, &L::compress_ary_bounded, &L::grind, &L::absorb, &L::absorb_varlen, &L::squeeze,
                                       &Engine::lds_bytes, &L::describe};
     return ops;
 }
@@ -1175,6 +1233,10 @@ const EngineOps *window_ops(uint32_t t);   // nullptr for a width the translatio
 #error "PMX_TU = 99 (make asm1) names its engine with -DPMX_ONE_T=<width> -DPMX_ONE_ALPHA=<5 | 0>"
 #endif
 template __global__ void permute_kernel<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>(const DevConfig, const uint32_t *__restrict__, uint64_t *__restrict__, size_t);
+#ifdef PMX_ONE_GRIND    // (make asm1 ... EXTRA=-DPMX_ONE_GRIND: the grind kernel of the same engine as well)
+template __global__ void grind_kernel<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>(const DevConfig, const uint32_t *__restrict__, const uint64_t *__restrict__, uint32_t, uint32_t,
+                                                                                uint64_t, size_t, uint64_t *__restrict__);
+#endif
 #ifdef PMX_ONE_RAGGED   // (make asm1 ... EXTRA=-DPMX_ONE_RAGGED: the two ragged pass kernels of the same engine as well)
 hipError_t one_ragged(const DevConfig &c, uint64_t *s, uint32_t *tg, uint32_t *ix, uint64_t *io, const uint64_t *o, size_t n, const PassScratch &p) {
     return Launch<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>::template sponge_passes<false>(c, PMX_ONE_T, s, tg, ix, io, RowsRagged{io, o, 8}, n, 0, p);
@@ -1243,7 +1305,9 @@ static const EngineOps *select_engine(const DevConfig &c, uint32_t t, int op, si
         case PMX_OP_ABSORB:
         case PMX_OP_SQUEEZE:
         // (the split (rate 3, capacity 0) of the same width takes the one-lane-per-state engine at every tree level)
-        case PMX_OP_COMPRESS: quad = quad_shape(c, t); break;
+        case PMX_OP_COMPRESS:
+        // (a chunk of n candidates addresses the state through capacity + index like a compression)
+        case PMX_OP_GRIND: quad = quad_shape(c, t); break;
         default: return nullptr;
     }
     if (quad && n <= kQuadMaxUnits) return by_alpha<QuadEngine>(c);
@@ -1277,6 +1341,13 @@ hipError_t launch_compress_level(const DevConfig &c, uint32_t t, const uint64_t 
     const size_t n = n_children / arity + (n_children % arity ? 1 : 0);
     if (n_children % arity == 0) return launch_compress_ary(c, t, in, out, arity, n, st);
     return select_engine(c, t, PMX_OP_COMPRESS, n)->compress_ary_bounded(c, t, in, out, arity, n_children, n, st);
+}
+// One chunk of a grinding search (grind_kernel): the n nonces first .. first + n - 1 against the base state at `base`, index < rate;
+// *best is lowered to the smallest accepted one.  (An index at or beyond the rate would address past the state: refused here too.)
+hipError_t launch_grind(const DevConfig &c, uint32_t t, const uint64_t *base, uint32_t index, uint32_t bits, uint64_t first, size_t n,
+                        uint64_t *best, hipStream_t st) {
+    if (index >= c.rounds.rate || n == 0 || n > (size_t)0x7fffffff * 64 || first + (uint64_t)(n - 1) < first) return hipErrorInvalidValue;
+    return select_engine(c, t, PMX_OP_GRIND, n)->grind(c, t, base, index, bits, first, n, best, st);
 }
 hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch) {

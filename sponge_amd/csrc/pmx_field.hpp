@@ -113,9 +113,9 @@ struct FieldRt {
     uint32_t p[kN];       // modulus, 29-bit limbs
     uint32_t pinv;        // -p^-1 mod 2^29
     uint32_t unit;        // 1, as a run-time value: x * unit + acc is a single v_mad_u64_u32 (mont_mul_add, tab_col_end)
-    const uint32_t *io;   // kIoWords words: [p as 8 x 32-bit limbs | 2^266 mod p | 2^256 mod p (9 x 29-bit limbs each)]
+    const uint32_t *io;   // kIoWords words: [p as 8 x 32-bit limbs | 2^266 mod p | 2^256 mod p | 2^517 mod p (9 x 29-bit limbs each)]
 };
-constexpr int kIoP32 = 0, kIoToInt = 8, kIoToAbi = 8 + kN, kIoWords = 28;
+constexpr int kIoP32 = 0, kIoToInt = 8, kIoToAbi = 8 + kN, kIoFromU64 = 28, kIoWords = 40;
 
 #if defined(PMX_HOSTCHECK) && !defined(__HIPCC__)
 void hostcheck_track(int tag, const Fe &x, const FieldRt &f);   // defined in tests/hostcheck/pmx_hostcheck.cpp
@@ -618,6 +618,31 @@ PMX_FN Abi abi_to_canonical(const Abi &a, const FieldRt &f) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) r.w[i] = borrow ? v.w[i] : d[i];
     return r;
+}
+
+// The converse of abi_to_canonical for a machine integer: v -> the ABI residue v * 2^256 mod p, fully reduced - what ark-ff's F::from(v)
+// holds (the nonce a grinding search absorbs, pmx_device.hip: grind_kernel).  One Montgomery product of the three limbs of v with
+// 2^517 mod p (io + kIoFromU64): v * 2^517 * 2^-261.  T = v * c < 2^64 p gives a norm result below p + 1: one conditional subtraction
+// (fe_to_abi_scaled makes two).
+PMX_FN Abi abi_from_u64(uint64_t v, const FieldRt &f) {
+    Fe a = fe_zero();
+    a.l[0] = (uint32_t)v & kMask;
+    a.l[1] = (uint32_t)(v >> kW) & kMask;
+    a.l[2] = (uint32_t)(v >> (2 * kW));
+    return fe_to_abi_scaled(mont_mul(a, fe_const(f.io + kIoFromU64), f), f);
+}
+
+// the low `bits` bits of a canonical integer are all zero (squeeze_bits(bits) is all false for bits below the modulus bit length,
+// src/poseidon/mod.rs:272-286: the bits of the first squeezed element, little-endian); bits <= 256
+PMX_FN bool canonical_low_bits_zero(const Abi &x, uint32_t bits) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t lo = 32u * (uint32_t)i;
+        const uint32_t mask = bits >= lo + 32 ? 0xffffffffu : bits > lo ? (1u << (bits - lo)) - 1u : 0u;
+        any |= x.w[i] & mask;
+    }
+    return any == 0;
 }
 
 #if defined(__HIPCC__)

@@ -23,6 +23,11 @@ hipError_t launch_compress_ary(const DevConfig &c, uint32_t t, const uint64_t *i
 // by the arity is launch_compress_ary.
 hipError_t launch_compress_level(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
                                  hipStream_t st);
+// one chunk of a proof-of-work search (pmx_sponge_grind): the nonces first .. first + n - 1 tried against the one base state at `base`
+// ([t][4], device) with the nonce absorbed at state[capacity + index], index < rate; best[0] (device, UINT64_MAX before the first chunk)
+// is lowered to the smallest nonce whose digest has `bits` low zero bits and best[1] (0 before) is set to 1 with it.  No per-candidate memory.
+hipError_t launch_grind(const DevConfig &c, uint32_t t, const uint64_t *base, uint32_t index, uint32_t bits, uint64_t first, size_t n,
+                        uint64_t *best, hipStream_t st);
 // Device scratch for the pass lists of the drivers that run as passes (pmx_device.hip: sponge_passes): `get` hands out at least
 // `bytes` bytes that stay valid for everything enqueued on `st` by this call, `done` is called once behind the call's last launch
 // (pmx_api.cpp: a pool of blocks owned by the context, each released by an event recorded there).  Engines that need no lists
@@ -66,6 +71,8 @@ struct EngineOps {
     // (the level with a short last row: n = ceil(n_children / arity) parents, children bounded by n_children)
     hipError_t (*compress_ary_bounded)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
                                        size_t n, hipStream_t st);
+    hipError_t (*grind)(const DevConfig &c, uint32_t t, const uint64_t *base, uint32_t index, uint32_t bits, uint64_t first, size_t n,
+                        uint64_t *best, hipStream_t st);
     hipError_t (*absorb)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,
                          size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch);
     hipError_t (*absorb_varlen)(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in,

@@ -368,6 +368,28 @@ public:
         return bits;
     }
 
+    // Proof-of-work grinding (pmx_sponge_grind; no counterpart in the reference): the smallest nonce v of [first, first + count) for which
+    // a clone of this sponge that absorbs F::from(v) squeezes `bits` zero bits, or nullopt.  bits < MODULUS_BIT_SIZE.  About 2^bits
+    // permutations of this one state, on the device; the sponge itself is not modified - absorb the winner to go on.
+    // count = UINT64_MAX (the default): to the end of the 64-bit nonces.
+    std::optional<uint64_t> grind(uint32_t bits, uint64_t first = 0, uint64_t count = UINT64_MAX) const {
+        if (count == UINT64_MAX && first) count = UINT64_MAX - first + 1;
+        uint64_t nonce = 0;
+        int found = 0;
+        check(pmx_sponge_grind(parameters.context(device_)->get(), state[0].l.data(), mode.tag, (uint32_t)mode.index, bits, first, count,
+                               &nonce, &found));
+        return found ? std::optional<uint64_t>(nonce) : std::nullopt;
+    }
+    // The acceptance rule itself, through the existing entries on a copy of this sponge: absorb(F::from(nonce)); squeeze_bits(bits)
+    // all false (mod.rs:232-254, 272-286).  What a verifier runs: two host-buffer calls of one sponge.
+    bool check_pow(uint64_t nonce, size_t bits) const {
+        PoseidonSponge c = *this;
+        c.absorb(std::vector<Fp>{fp_from_u64(parameters.field, nonce)});   // Fr::from(nonce)
+        for (bool b : c.squeeze_bits(bits))
+            if (b) return false;
+        return true;
+    }
+
     // squeeze_field_elements_with_sizes::<F2> (mod.rs:288-304).  Same characteristic: the native path below.
     // Otherwise the default of src/lib.rs:61-100: one squeeze_bits call for all elements, num_bits::<F2>() bits each,
     // little-endian, through from_le_bytes_mod_order (the value is < 2^(bits(p2)-1) <= p2, so nothing is reduced).

@@ -276,6 +276,17 @@ class Context:
                                                             _ptr(out) if out.size else None, num_bits, n))
         return out.view(np.bool_)
 
+    def sponge_grind(self, state: np.ndarray, tag: int, index: int, bits: int, first: int = 0, count: Optional[int] = None) -> Optional[int]:
+        """The smallest nonce v of [first, first + count) for which the sponge (state [t][4], tag, index), after absorbing F::from(v),
+        squeezes `bits` zero bits (pmx_sponge_grind), or None.  count None: to the end of the 64-bit nonces (one call takes at most
+        2^64 - 1 candidates).  `state` is not modified."""
+        state = np.ascontiguousarray(state, dtype=np.uint64)
+        if count is None:
+            count = min((1 << 64) - first, (1 << 64) - 1)
+        nonce, found = ctypes.c_uint64(0), ctypes.c_int(0)
+        _lib.check(_lib.lib().pmx_sponge_grind(self._h, _ptr(state), tag, index, bits, first, count, ctypes.byref(nonce), ctypes.byref(found)))
+        return nonce.value if found.value else None
+
     def hash_varlen_batch(self, elems, offsets=None, out_len: int = 1) -> np.ndarray:
         """Per row i: new; absorb(elems[offsets[i] .. offsets[i+1]]); squeeze_native(out_len) (pmx_hash_varlen_batch).  `elems` is
         [*][4] with `offsets` [n+1], or a list of [L_i][4] arrays (offsets None).  Returns [n][out_len][4]."""
@@ -554,6 +565,21 @@ class PoseidonSponge:
             elems = input
         elems = np.ascontiguousarray(elems, dtype=np.uint64).reshape(1, -1, 4)
         self._b.absorb(elems)
+
+    def grind(self, bits: int, first: int = 0, count: Optional[int] = None) -> Optional[int]:
+        """Proof-of-work grinding (pmx_sponge_grind; no counterpart in the reference): the smallest nonce v of [first, first + count)
+        - count None: to the end of the 64-bit nonces - such that  c = self.clone(); c.absorb(F::from(v)); c.squeeze_bits(bits)  is all false, or None.
+        bits < MODULUS_BIT_SIZE.  About 2^bits permutations of this one state, fused on the device; the sponge is not modified -
+        absorb the winner (self.absorb(field.from_ints([v]))) to go on with the transcript."""
+        return self.parameters.context(self._b.device).sponge_grind(self._b.state[0], int(self._b.mode_tag[0]), int(self._b.mode_index[0]),
+                                                                    bits, first, count)
+
+    def check_pow(self, nonce: int, bits: int) -> bool:
+        """The acceptance rule itself, through the existing absorb and squeeze-bits entries on a copy of this sponge (what a verifier
+        runs): absorb(F::from(nonce)); squeeze_bits(bits) all false (mod.rs:232-254, 272-286)."""
+        c = self._b.clone()
+        c.absorb(self.parameters.field.from_ints([nonce]).reshape(1, 1, 4))
+        return not c.squeeze_bits(bits).any()
 
     def fork(self, domain: bytes) -> "PoseidonSponge":
         """CryptographicSponge::fork (src/lib.rs:149-157): clone, then absorb len(domain) as usize bytes ++ domain,
