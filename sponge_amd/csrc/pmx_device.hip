@@ -31,9 +31,9 @@
 #include "pmx_permute.hpp"
 #include "pmx_sponge_plan.hpp"
 
-// The file is compiled five times (Makefile, in parallel): PMX_TU = 0 holds the quad engine, the run-time-width engine and the
+// The file is compiled nine times (Makefile, in parallel): PMX_TU = 0 holds the quad engine, the run-time-width engine and the
 // public launchers; PMX_TU = 1 / 3 hold the hybrid engines for alpha = 5 (widths up to 6 / from 7), PMX_TU = 2 / 4 the same for the
-// generic S-box (each width x 7 kernels - by far the longest compile).
+// generic S-box (each width x 7 kernels - by far the longest compile), PMX_TU = 5 .. 8 those four for a modulus that is 1 mod 2^29.
 #ifndef PMX_TU
 #define PMX_TU 0
 #endif
@@ -299,6 +299,18 @@ struct HybridEngine : LanePerUnit<64 * kMfmaWaves> {
     // lane0_zero: the caller knows lane 0 of the state is zero (pmx_permute.hpp: the window engines skip its round-0 S-box)
     __device__ __forceinline__ void permute(uint32_t want_lo = 0, uint32_t want_hi = T, bool lane0_zero = false) {
         permute_hybrid<T, ALPHA, Scratch, mfma_window_for(T)>(s, sc, tb, c, one, f, want_lo, want_hi, lane0_zero);
+    }
+};
+
+// The same engine for a modulus that is 1 mod 2^29 (BLS12-381 Fr): its S-boxes take the complemented quotient digits (pmx_field.hpp:
+// mont_sqr_p1 / mont_mul_p1), everything else - tables, rows, I/O, the name it reports - is HybridEngine's.  The launcher's choice
+// (window_engine below); a kernel of it must never meet another modulus.
+template <int T, int ALPHA>
+struct HybridEngineP1 : HybridEngine<T, ALPHA> {
+    using Base = HybridEngine<T, ALPHA>;
+    __device__ __forceinline__ HybridEngineP1(const DevConfig &d, const uint32_t *consts) : Base(d, consts) {}
+    __device__ __forceinline__ void permute(uint32_t want_lo = 0, uint32_t want_hi = T, bool lane0_zero = false) {
+        permute_hybrid<T, ALPHA, typename Base::Scratch, mfma_window_for(T), true>(this->s, this->sc, this->tb, this->c, this->one, this->f, want_lo, want_hi, lane0_zero);
     }
 };
 
@@ -1222,9 +1234,10 @@ static const EngineOps &engine_ops() {
     return ops;
 }
 
-// ---- window engines: four translation units (they dominate the build time, so they compile in parallel), the exponent (1, 3: alpha = 5;
-// 2, 4: any other, ALPHA = 0) x the widths (1, 2: t = 3 .. 6; 3, 4: t = 7 .. 9).  Each exports the lookup of its own half:
-template <int ALPHA, bool WIDE>
+// ---- window engines: eight translation units (they dominate the build time, so they compile in parallel), the exponent (1, 3: alpha = 5;
+// 2, 4: any other, ALPHA = 0) x the widths (1, 2: t = 3 .. 6; 3, 4: t = 7 .. 9), and 5 .. 8 the same four for a modulus that is 1 mod 2^29
+// (HybridEngineP1).  Each exports the lookup of its own part:
+template <int ALPHA, bool WIDE, bool P1>
 const EngineOps *window_ops(uint32_t t);   // nullptr for a width the translation unit does not hold
 
 #if PMX_TU == 99
@@ -1232,35 +1245,48 @@ const EngineOps *window_ops(uint32_t t);   // nullptr for a width the translatio
 #if !defined(PMX_ONE_T) || !defined(PMX_ONE_ALPHA)
 #error "PMX_TU = 99 (make asm1) names its engine with -DPMX_ONE_T=<width> -DPMX_ONE_ALPHA=<5 | 0>"
 #endif
-template __global__ void permute_kernel<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>(const DevConfig, const uint32_t *__restrict__, uint64_t *__restrict__, size_t);
+#ifdef PMX_ONE_P1   // (make asm1 ... EXTRA=-DPMX_ONE_P1: the engine of a modulus that is 1 mod 2^29)
+#define PMX_ONE_ENGINE HybridEngineP1<PMX_ONE_T, PMX_ONE_ALPHA>
+#else
+#define PMX_ONE_ENGINE HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>
+#endif
+template __global__ void permute_kernel<PMX_ONE_ENGINE>(const DevConfig, const uint32_t *__restrict__, uint64_t *__restrict__, size_t);
 #ifdef PMX_ONE_GRIND    // (make asm1 ... EXTRA=-DPMX_ONE_GRIND: the grind kernel of the same engine as well)
-template __global__ void grind_kernel<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>(const DevConfig, const uint32_t *__restrict__, const uint64_t *__restrict__, uint32_t, uint32_t,
+template __global__ void grind_kernel<PMX_ONE_ENGINE>(const DevConfig, const uint32_t *__restrict__, const uint64_t *__restrict__, uint32_t, uint32_t,
                                                                                 uint64_t, size_t, uint64_t *__restrict__);
 #endif
 #ifdef PMX_ONE_RAGGED   // (make asm1 ... EXTRA=-DPMX_ONE_RAGGED: the two ragged pass kernels of the same engine as well)
 hipError_t one_ragged(const DevConfig &c, uint64_t *s, uint32_t *tg, uint32_t *ix, uint64_t *io, const uint64_t *o, size_t n, const PassScratch &p) {
-    return Launch<HybridEngine<PMX_ONE_T, PMX_ONE_ALPHA>>::template sponge_passes<false>(c, PMX_ONE_T, s, tg, ix, io, RowsRagged{io, o, 8}, n, 0, p);
+    return Launch<PMX_ONE_ENGINE>::template sponge_passes<false>(c, PMX_ONE_T, s, tg, ix, io, RowsRagged{io, o, 8}, n, 0, p);
 }
 #endif
 #elif PMX_TU != 0
 // ---- window engines of this translation unit ------------------------------------------------------------------------
-constexpr int kTuAlpha = (PMX_TU == 1 || PMX_TU == 3) ? 5 : 0;
-constexpr bool kTuWide = PMX_TU >= 3;
+constexpr bool kTuP1 = PMX_TU >= 5;
+constexpr int kTuPart = kTuP1 ? PMX_TU - 4 : PMX_TU;
+constexpr int kTuAlpha = (kTuPart == 1 || kTuPart == 3) ? 5 : 0;
+constexpr bool kTuWide = kTuPart >= 3;
+template <int T>
+using TuEngine = std::conditional_t<kTuP1, HybridEngineP1<T, kTuAlpha>, HybridEngine<T, kTuAlpha>>;
 template <>
-const EngineOps *window_ops<kTuAlpha, kTuWide>(uint32_t t) {
+const EngineOps *window_ops<kTuAlpha, kTuWide, kTuP1>(uint32_t t) {
     const EngineOps *ops = nullptr;
     static_for<(kTuWide ? 7 : 3), (kTuWide ? 10 : 7)>([&](auto width) {
-        if (t == (uint32_t)width) ops = &engine_ops<HybridEngine<decltype(width)::value, kTuAlpha>>();
+        if (t == (uint32_t)width) ops = &engine_ops<TuEngine<decltype(width)::value>>();
     });
     return ops;
 }
 
 #else  // PMX_TU == 0
 // ---- public launchers -------------------------------------------------------------------------------------------------
-template <> const EngineOps *window_ops<5, false>(uint32_t t);
-template <> const EngineOps *window_ops<5, true>(uint32_t t);
-template <> const EngineOps *window_ops<0, false>(uint32_t t);
-template <> const EngineOps *window_ops<0, true>(uint32_t t);
+template <> const EngineOps *window_ops<5, false, false>(uint32_t t);
+template <> const EngineOps *window_ops<5, true, false>(uint32_t t);
+template <> const EngineOps *window_ops<0, false, false>(uint32_t t);
+template <> const EngineOps *window_ops<0, true, false>(uint32_t t);
+template <> const EngineOps *window_ops<5, false, true>(uint32_t t);
+template <> const EngineOps *window_ops<5, true, true>(uint32_t t);
+template <> const EngineOps *window_ops<0, false, true>(uint32_t t);
+template <> const EngineOps *window_ops<0, true, true>(uint32_t t);
 
 // the quad engine's table exists (t = 3, optimised schedule) and fits LDS; the lane of each element is fixed by the
 // split only where elements are addressed through capacity / rate (quad_shape below)
@@ -1274,12 +1300,17 @@ static bool quad_shape(const DevConfig &c, uint32_t t) { return quad_table(c, t)
 // chip better - profiles/r05/v_ab_t3_engine_threshold_32769.txt, w_ab_quad_kernels_up_to_16384_only_not_kept.txt).
 static constexpr size_t kQuadMaxUnits = 32768;
 
-// the window engine of the config and width (the exponent's half of the family, then the width's), if the config has its tables and
-// its LDS fits the device
+// the window engine of the config and width (the modulus' and the exponent's part of the family, then the width's), if the config has its
+// tables and its LDS fits the device.  A modulus that is 1 mod 2^29 (pmx_prepare.hpp records it: Prepared::unit_low_limb; here it is read off
+// the limbs the kernels get) takes the engines with the complemented quotient digits, every other modulus the generic step.
+template <bool P1>
+static const EngineOps *window_engine_of(const DevConfig &c, uint32_t t) {
+    return c.rounds.alpha == 5 ? (t <= 6 ? window_ops<5, false, P1>(t) : window_ops<5, true, P1>(t))
+                               : (t <= 6 ? window_ops<0, false, P1>(t) : window_ops<0, true, P1>(t));
+}
 static const EngineOps *window_engine(const DevConfig &c, uint32_t t) {
     if (!c.has_opt || !c.mfma_dense || t < (uint32_t)PMX_MFMA_MIN_T || t > (uint32_t)PMX_MFMA_MAX_T) return nullptr;
-    const EngineOps *w = c.rounds.alpha == 5 ? (t <= 6 ? window_ops<5, false>(t) : window_ops<5, true>(t))
-                                             : (t <= 6 ? window_ops<0, false>(t) : window_ops<0, true>(t));
+    const EngineOps *w = field_unit_low_limb(c.field.p) ? window_engine_of<true>(c, t) : window_engine_of<false>(c, t);
     return w && w->lds_bytes(c, t) <= (size_t)c.max_lds_bytes ? w : nullptr;
 }
 // the quad or run-time-width engine of the config's exponent

@@ -141,7 +141,9 @@ PMX_FN Fe fe_zero() {
 // acc + m_k p_0 = 0 mod 2^29 and leaves acc = (acc + m_k p_0) >> 29, the carry into the next column.
 // (A variant for p = 1 mod 2^29 - BLS12-381 Fr: m_k = -acc mod 2^29, carry = (acc + 2^29 - 1) >> 29, i.e. a subtract
 // and a 64-bit add in place of v_mul_lo_u32 and the multiply - measured +1.3 % on C2, +0.4 % on the hash driver and
-// -1 % on the Merkle tree; not kept.)
+// -1 % on the Merkle tree; not kept: it swapped kinds of instruction, five for four.  The S-boxes of such a modulus now take
+// mont_step_p1 below - complemented digits, TWO instructions a step; this generic step still serves every other modulus and,
+// for every modulus, the products outside the window engines' S-boxes.)
 PMX_FN uint32_t mont_step(uint64_t &acc, const FieldRt &f) {
     const uint32_t m = ((uint32_t)acc * f.pinv) & kMask;
     acc += (uint64_t)m * f.p[0];   // low 29 bits are now zero
@@ -304,6 +306,98 @@ PMX_FN Fe mont_sqr(const Fe &a, const FieldRt &f) {
     return out;
 }
 
+// ---- moduli with p = 1 mod 2^29 (BLS12-381 Fr, 2-adicity 32): COMPLEMENTED quotient digits ---------------------------------------
+// Then p_0 = 1 and -p^-1 = -1 mod 2^29: the digit of a column is the negated low limb of its accumulator, and the product m_k p_0 only
+// clears bits that are dropped anyway.  The step below takes the COMPLEMENT instead of the negative,
+//     n_k = ~acc & mask   (one v_bfi_b32),      acc >>= 29   (the carry as it stands: acc + n_k p_0 has the same bits above 29)
+// two instructions where mont_step has four, no multiply among them.  With N = sum n_k 2^(29 k) the low 261 bits of V + N p are then all
+// ONES, not zeros:  V + N p + 1 = (R + 1) 2^261  for the integer R that comes out of the upper columns - the result is off by one at both
+// ends.  The two ones are put back where an instruction slot or a cheap one exists (E = 1: the digit of column 0 counts one more in the
+// products of the later columns, m_0 = n_0 + 1 = -acc mod 2^29 in [1, 2^29] - one v_add_u32):
+//     kP1In    V as it is, E = 1:    V + (N + 1) p = (R + 1) 2^261;  returns R with limb 0 + 1 - the true value, limb 0 in [1, 2^29]
+//     kP1Sq    a.l[0] >= 1 (an operand that came from kP1In / kP1Sq), column 0 opens with a_0 a_0 - 1 >= 0 - the -1 is the free addend of
+//              the column's first v_mad_u64_u32 -, E = 0:   V + N p = (R + 1) 2^261;  returns R with limb 0 + 1 as well
+//     kP1Out   E = 1 and 2^29 added to column 8 before its carry leaves (a 64-bit add):  V + (N + 1) p = R 2^261 - R itself, every limb
+//              below 2^29: what the byte cut of the matrix-core layers and every other consumer of an S-box output takes
+// In every form the value returned is (V + M p) / 2^261 with M <= 2^261: norm (limb 0 <= 2^29 for the first two), B <= V / (p 2^261) + 1 -
+// mont_step's bound - and congruent to V 2^-261 with NO offset, so no constant of the host changes.  A column sums what it summed before
+// without the m_k p_0 product; m_0 <= 2^29 and an operand limb 0 <= 2^29 keep every product inside the 2^58 / 2^59 / 2^61 it had
+// (tests/test_p1_step.py replays the worst case of every call site).  x^5 = kP1In, kP1Sq, kP1Out: 6 x 9 steps lose two instructions each,
+// five come back (two m_0, two limb-0 increments, one 64-bit add).
+// (The variant measured earlier - m_k = -acc mod 2^29, carry = (acc + 2^29 - 1) >> 29, see mont_step - kept the low bits ZERO and paid a
+// subtract and a two-instruction 64-bit add per step, five instructions against four: it changed the kind of instruction, not the count.)
+enum { kP1In = 0, kP1Sq = 1, kP1Out = 2 };
+PMX_FN constexpr bool field_unit_low_limb(const uint32_t (&p)[kN]) { return p[0] == 1u; }   // p = 1 mod 2^29 (p is odd and below 2^255)
+
+PMX_FN uint32_t mont_step_p1(uint64_t &acc) {
+    const uint32_t n = ~(uint32_t)acc & kMask;
+    acc >>= kW;
+    return n;
+}
+
+// a * b * 2^-261, a lazy, b norm (mont_mul's operands); kP1Out
+PMX_FN Fe mont_mul_p1(const Fe &a, const Fe &b, const FieldRt &f) {
+    uint32_t m[kN];
+    Fe out;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * kN - 1; ++k) {
+        const int lo_i = k < kN ? 0 : k - (kN - 1);
+        const int hi_i = k < kN ? k : kN - 1;
+#pragma unroll
+        for (int i = lo_i; i <= hi_i; ++i) acc += (uint64_t)a.l[i] * b.l[k - i];
+#pragma unroll
+        for (int j = lo_i; j <= hi_i; ++j) {
+            if (j < k || k >= kN) acc += (uint64_t)m[j] * f.p[k - j];
+        }
+        if (k < kN) {
+            if (k == kN - 1) acc += (uint64_t)1 << kW;
+            m[k] = mont_step_p1(acc);
+            if (k == 0) m[0] += 1;
+        } else {
+            out.l[k - kN] = (uint32_t)acc & kMask;
+            acc >>= kW;
+        }
+    }
+    out.l[kN - 1] = (uint32_t)acc;
+    return out;
+}
+
+// a^2 * 2^-261 (mont_sqr's operand: lazy; MODE = kP1Sq: limb 0 >= 1)
+template <int MODE>
+PMX_FN Fe mont_sqr_p1(const Fe &a, const FieldRt &f) {
+    uint32_t d[kN];  // 2 * a_j
+#pragma unroll
+    for (int i = 0; i < kN; ++i) d[i] = a.l[i] << 1;
+    uint32_t m[kN];
+    Fe out;
+    uint64_t acc = MODE == kP1Sq ? ~(uint64_t)0 : (uint64_t)0;   // kP1Sq: a_0 a_0 - 1, not negative
+#pragma unroll
+    for (int k = 0; k < 2 * kN - 1; ++k) {
+#pragma unroll
+        for (int i = 0; i < kN; ++i) {
+            const int j = k - i;
+            if (j > i && j < kN) acc += (uint64_t)a.l[i] * d[j];
+        }
+        if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
+        if (k < kN) {
+#pragma unroll
+            for (int j = 0; j < k; ++j) acc += (uint64_t)m[j] * f.p[k - j];
+            if (MODE == kP1Out && k == kN - 1) acc += (uint64_t)1 << kW;
+            m[k] = mont_step_p1(acc);
+            if (MODE != kP1Sq && k == 0) m[0] += 1;
+        } else {
+#pragma unroll
+            for (int j = k - (kN - 1); j < kN; ++j) acc += (uint64_t)m[j] * f.p[k - j];
+            out.l[k - kN] = (uint32_t)acc & kMask;
+            acc >>= kW;
+        }
+    }
+    out.l[kN - 1] = (uint32_t)acc;
+    if (MODE != kP1Out) out.l[0] += 1;
+    return out;
+}
+
 // ---- products by CONSTANTS: shifted tables -----------------------------------------------------------------------
 // For a constant C the host stores the nine residues  T_j = C * 2^(29 j + 58) mod p  (canonical, 9 limbs each), a row
 // of N constants in consumption order (layout below).  Then for any element z (internal form, limbs z_j)
@@ -447,9 +541,32 @@ PMX_FN Fe cols_redc(Cols &t, const FieldRt &f, const Fe *s = nullptr) {
 // square-and-multiply seeded with x (alpha is wave-uniform, so the branches are scalar).
 // x may be lazy with B <= 4, or norm with B < 7.6 (a window S-box input with a small-integer history term, pmx_permute.hpp: B^2 < 2^261 / p);
 // the result is norm with B < 1.3 (alpha >= 4; pmx_prepare.hpp: opt_schedule_lane_headroom has the smaller exponents).  `one` = 2^261 mod p.
-template <int ALPHA>
+// P1: the modulus is 1 mod 2^29 and the products take the complemented digits (mont_sqr_p1 / mont_mul_p1 above): same values mod p, same bounds.
+template <int ALPHA, bool P1 = false>
 PMX_FN Fe fe_sbox(const Fe &x, uint64_t alpha, const Fe &one, const FieldRt &f) {
-    if constexpr (ALPHA == 5) {
+    if constexpr (P1 && ALPHA == 5) {
+        const Fe x2 = mont_sqr_p1<kP1In>(x, f);
+        const Fe x4 = mont_sqr_p1<kP1Sq>(x2, f);
+        return mont_mul_p1(x4, x, f);
+    } else if constexpr (P1 && ALPHA == 17) {
+        Fe y = mont_sqr_p1<kP1In>(x, f);
+        y = mont_sqr_p1<kP1Sq>(y, f);
+        y = mont_sqr_p1<kP1Sq>(y, f);
+        y = mont_sqr_p1<kP1Sq>(y, f);
+        return mont_mul_p1(y, x, f);
+    } else if constexpr (P1) {
+        // any exponent: which product is the last one is known at run time only, so every one of them returns the normalised form
+        if (alpha == 0) return one;
+        if (alpha == 1) return mont_mul_p1(x, one, f);
+        const int top = 63 - __builtin_clzll(alpha);
+        Fe acc = mont_sqr_p1<kP1Out>(x, f);
+        if ((alpha >> (top - 1)) & 1) acc = mont_mul_p1(acc, x, f);
+        for (int bit = top - 2; bit >= 0; --bit) {
+            acc = mont_sqr_p1<kP1Out>(acc, f);
+            if ((alpha >> bit) & 1) acc = mont_mul_p1(acc, x, f);
+        }
+        return acc;
+    } else if constexpr (ALPHA == 5) {
         const Fe x2 = mont_sqr(x, f);
         const Fe x4 = mont_sqr(x2, f);
         return mont_mul(x4, x, f);

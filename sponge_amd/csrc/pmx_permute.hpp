@@ -56,7 +56,7 @@ PMX_FN uint32_t full_ordinal(uint32_t r, const Rounds &c) { return r < c.half_fu
 //   lane0_zero     the caller knows that s[0] is zero on entry - the capacity lane of a fresh sponge - so the S-box of that lane in
 //                  round 0 is a constant of the config, stored behind the window tables: one S-box of 55 fewer per 2-to-1 compression at t = 3.
 // Every lane of the wave must be here (the rows exchange operands between the lanes of a pair).
-template <int T, int ALPHA, class Scratch, int MFMA_WINDOW>
+template <int T, int ALPHA, class Scratch, int MFMA_WINDOW, bool P1 = false>
 PMX_FN void permute_hybrid(Fe (&s)[T], Scratch &sc, const OptTables &tb, const Rounds &c, const Fe &one,
                            const FieldRt &f, uint32_t want_lo = 0, uint32_t want_hi = T, bool lane0_zero = false) {
     static_assert(MFMA_WINDOW > 0 && MFMA_WINDOW <= T, "a window is at most as long as the state is wide");
@@ -84,14 +84,14 @@ PMX_FN void permute_hybrid(Fe (&s)[T], Scratch &sc, const OptTables &tb, const R
                     MfmaHistRow<T> hr;
                     constexpr bool kFetchAhead = T != 5 && T != 9;   // (t = 5 sits on the 168 registers of three waves per SIMD, t = 9 carries 136 operand words: the 16 of a fetched-ahead table spill)
                     if constexpr (K > 2 && kFetchAhead) hr.template load<2>(hist);
-                    Fe z = fe_sbox<ALPHA>(s[0], c.alpha, one, f);                 // z_1 = x_1^alpha: x_1 came whole out of the layer before
+                    Fe z = fe_sbox<ALPHA, P1>(s[0], c.alpha, one, f);                 // z_1 = x_1^alpha: x_1 came whole out of the layer before
                     mfma_cut_operand(z, &W[8 * (T - 1)]);
                     Fe x = fe_add_lazy(s[1], z);                                  // x_2 = z_1 + u_1
                     static_for<2, K + 1>([&](auto kk) {
                         constexpr int k = decltype(kk)::value;                    // S-box k, and in front of it the row of x_{k+1}
                         if ((uint32_t)k <= kw) {
                             const bool row = k < K && (uint32_t)k < kw;           // (wave-uniform)
-                            z = fe_sbox<ALPHA>(x, c.alpha, one, f);
+                            z = fe_sbox<ALPHA, P1>(x, c.alpha, one, f);
                             mfma_cut_operand(z, &W[8 * (T - 2 + k)]);
                             if constexpr (k < K) {
                                 // The row's products are issued BEHIND S-box k, its A operand having been fetched in front of it: issued in
@@ -117,7 +117,7 @@ PMX_FN void permute_hybrid(Fe (&s)[T], Scratch &sc, const OptTables &tb, const R
                     static_assert(K <= 3, "the table form of the history terms covers the single term of a window of three");
                     Fe in[NIN];
                     static_for<1, T>([&](auto i) { in[i - 1] = s[i]; });
-                    in[T - 1] = fe_sbox<ALPHA>(s[0], c.alpha, one, f);               // z_1 = x_1^alpha: x_1 came whole out of the layer before
+                    in[T - 1] = fe_sbox<ALPHA, P1>(s[0], c.alpha, one, f);               // z_1 = x_1^alpha: x_1 came whole out of the layer before
                     static_for<1, K>([&](auto kk) {
                         constexpr int k = decltype(kk)::value;                        // z_{k+1} from x_{k+1} = z_k + u_k + sum_{i<k} h_{k,i} z_i
                         if ((uint32_t)k < kw) {
@@ -139,7 +139,7 @@ PMX_FN void permute_hybrid(Fe (&s)[T], Scratch &sc, const OptTables &tb, const R
                             }
                             x = fe_add_lazy(x, in[T - 2 + k]);
                             if (small_sum) x = fe_normalize(x);        // (below 7.6 p: (7.6 p)^2 < p 2^261 for every p < 2^255)
-                            in[T - 1 + k] = fe_sbox<ALPHA>(x, c.alpha, one, f);
+                            in[T - 1 + k] = fe_sbox<ALPHA, P1>(x, c.alpha, one, f);
                         } else {
                             in[T - 1 + k] = fe_zero();
                         }
@@ -161,8 +161,8 @@ PMX_FN void permute_hybrid(Fe (&s)[T], Scratch &sc, const OptTables &tb, const R
         }
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
         for (uint32_t i = first; i + 1 < (uint32_t)T; ++i)
-            sc.set(i, fe_sbox<ALPHA>(fe_add_lazy(sc.get(i), fe_const(rk + i * kFeStride)), c.alpha, one, f));
-        s[T - 1] = fe_sbox<ALPHA>(fe_add_lazy(s[T - 1], fe_const(rk + (T - 1) * kFeStride)), c.alpha, one, f);
+            sc.set(i, fe_sbox<ALPHA, P1>(fe_add_lazy(sc.get(i), fe_const(rk + i * kFeStride)), c.alpha, one, f));
+        s[T - 1] = fe_sbox<ALPHA, P1>(fe_add_lazy(s[T - 1], fe_const(rk + (T - 1) * kFeStride)), c.alpha, one, f);
         static_for<0, T - 1>([&](auto i) { s[i] = sc.get(i); });
         // its layer: the round's own matrix - or, behind the entrance round, the windows' entry layer (same code, other table);
         // the last round's output is the permutation's

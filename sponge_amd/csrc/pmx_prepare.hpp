@@ -58,6 +58,7 @@ struct Prepared {
     size_t win_offset;
     uint32_t mfma_window;   // K, or 0: no windows (the sparse layers run on the VALU)
     size_t io_offset;   // kIoWords words behind FieldRt::io
+    bool unit_low_limb; // p = 1 mod 2^29: the window engines with the complemented quotient digits serve it (pmx_field.hpp: mont_sqr_p1)
 };
 
 // One dense layer as the A operands of pmx_mfma.hpp: `rows` = t rows of t constants (ABI Montgomery residues, row-major).
@@ -865,6 +866,7 @@ inline int prepare(const pmx_config *cfg, Prepared &out, std::string &err) {
     f.unit = 1;
     to_limbs29(hf.p, f.p);
     f.pinv = (uint32_t)hf.inv & kMask;
+    out.unit_low_limb = field_unit_low_limb(f.p);
     // constants of the ABI conversions (FieldRt::io)
     out.io_offset = out.consts.size();
     out.consts.resize(out.io_offset + kIoWords, 0u);
