@@ -339,7 +339,8 @@ int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, 
  * last).  The container itself lives upstream (ark-crypto-primitives), not in arkworks-rs/sponge; a parent is
  * (new; absorb([left, right]); squeeze_native(1))[0] as above.  depth = log2(n_leaves).
  * pmx_merkle_paths: host-only gather - paths_out [k][depth][4] receives, for each indices[i], the sibling of the leaf and
- * of each ancestor, bottom-up.
+ * of each ancestor, bottom-up.  Every index is checked before anything is written (as pmx_merkle_ary_paths and
+ * pmx_merkle_ragged_paths do): a call refused with "out of range" leaves paths_out untouched.
  * pmx_merkle_verify_paths: k paths at once - one upload, `depth` level steps on the device (each a batched 2-to-1
  * compression of all k running nodes), one download: ok_out[i] = 1 iff hashing leaves[i] up its path (indices[i] says
  * left / right at each level) gives `root` and indices[i] < 2^depth.

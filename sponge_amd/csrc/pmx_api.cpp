@@ -20,7 +20,6 @@
 #include "pmx_prepare.hpp"
 #include "pmx_launch.hpp"
 #include "pmx_grind_plan.hpp"
-#include "pmx_merkle_plan.hpp"
 #include "pmx_sponge_plan.hpp"
 #include "pmx_squeeze_cut.hpp"
 
@@ -44,7 +43,9 @@ int hip_fail(hipError_t e, const char *what) {
 
 using namespace pmx;
 
-static int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
+namespace pmx {
+
+int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
     if (bytes == 0) bytes = 16;
     if (ctx->scratch_bytes[slot] < bytes) {
         void *old = ctx->scratch[slot];
@@ -58,16 +59,7 @@ static int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
     return PMX_OK;
 }
 
-// Host-buffer entry points queue asynchronous copies that read and write the CALLER's memory: whatever way they
-// leave (including an error half way through), nothing may still be in flight on the context's streams.
-struct StreamDrain {
-    pmx_ctx *ctx;
-    ~StreamDrain() {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream2);
-        (void)hipStreamSynchronize(ctx->stream3);
-    }
-};
+}  // namespace pmx
 
 // The host-buffer pipeline of a batch whose buffers are page-locked: chunk i is uploaded on `stream`, computed on `stream2` behind the
 // upload's event and downloaded on `stream3` behind the kernel's - the two copy directions have a stream (and a DMA engine) each, so chunk
@@ -374,7 +366,6 @@ extern "C" int pmx_ctx_engine_info(const pmx_ctx *ctx, int op, size_t n, size_t 
     return PMX_OK;
 }
 
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 // the argument lines the batch *_dev entries share, in the order each of them tests them (a null pointer counts as aligned)
 static int dev_batch_args(const void *a, const void *b, size_t n) {
     if (!aligned16(a) || !aligned16(b)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
@@ -1067,614 +1058,4 @@ extern "C" int pmx_sponge_absorb_varlen_batch(pmx_ctx *ctx, uint64_t *states, ui
 
 extern "C" int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uint64_t *offsets, uint64_t *out, size_t out_len, size_t n) {
     return varlen_host(ctx, nullptr, nullptr, nullptr, in, offsets, true, out, out_len, n, "pmx_hash_varlen_batch");
-}
-
-// ---- Merkle 2-to-1 -------------------------------------------------------------------------------
-// one permutation compresses at most `rate` children (absorbing more into a fresh sponge permutes in between: a hash row)
-static int arity_fits(const pmx_ctx *ctx, uint32_t arity) {
-    if (arity == 2 && ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
-    if (arity > ctx->dev.rounds.rate)
-        return set_error(PMX_ERR_CONFIG, "arity %u exceeds the rate %u: more children than the rate is a hash row (pmx_hash_batch_dev), not a single compression",
-                         arity, ctx->dev.rounds.rate);
-    return PMX_OK;
-}
-// Level by level on the caller's stream: level l reads the n_leaves >> (l-1) nodes of level l-1 and writes
-// n_leaves >> l parents.  (Cutting the tree into subtrees on concurrent streams was measured SLOWER - 7.0 ms ->
-// 12.5 ms at 8 streams for 2^21 leaves - because the narrow levels are latency-bound, not launch-bound.)
-// A single tree is the forest below with n_trees = 1: this is the level loop of both, behind each entry's own shape checks - and of the
-// trees of any arity further down (pmx_merkle_ary*: level l is n_leaves / arity^l parents; arity 2 launches the 2-to-1 kernel).
-static int merkle_levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t total_leaves, uint32_t arity, void *stream) {
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (!aligned16(d_nodes)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    size_t src = 0, width = total_leaves;
-    while (width > n_trees) {      // level l of all trees: [src, src + width) -> [src + width, src + width + width / arity)
-        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_nodes + src * 4, d_nodes + (src + width) * 4, arity, width / arity, (hipStream_t)stream));
-        src += width;
-        width /= arity;
-    }
-    return PMX_OK;
-}
-// Host buffers (the caller has bound the device): upload the leaves, the levels, download all nodes and / or the last n_trees (the roots).
-static int merkle_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t total_leaves, size_t n_nodes, uint32_t arity, uint64_t *nodes,
-                       uint64_t *roots) {
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d, leaves, total_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = merkle_levels_dev(ctx, (uint64_t *)d, n_trees, total_leaves, arity, ctx->stream))) return rc;
-    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (roots) PMX_HIP(hipMemcpyAsync(roots, (uint64_t *)d + (n_nodes - n_trees) * 4, n_trees * 32, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
-}
-
-extern "C" int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream) {
-    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_dev: null pointer");
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
-    return merkle_levels_dev(ctx, d_nodes, 1, n_leaves, 2, stream);
-}
-
-extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint64_t *nodes, uint64_t *root) {
-    PMX_ABI_BEGIN("pmx_merkle_2to1")
-    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1: null pointer");
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
-    PMX_BIND(ctx);
-    if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-    return merkle_host(ctx, leaves, 1, n_leaves, 2 * n_leaves - 1, 2, nodes, root);
-    PMX_ABI_END
-}
-
-// ---- many trees at once ------------------------------------------------------------------------------
-// The levels of ONE tree narrow down to a single compression, and a level of at most 16384 compressions costs the same 65 us
-// whatever its width (one permutation's dependent chain): 15 such levels are a quarter of a 2^21-leaf tree's
-// time.  n_trees trees of the same size advance TOGETHER, level by level: with the leaves laid out tree after tree, level l of
-// every tree is one contiguous array, its pairs never straddle two trees (leaves_per_tree is a power of two), and the narrowest
-// level launched is n_trees compressions wide.  It is the first log2(leaves_per_tree) levels of one tree over all the leaves.
-static int forest_shape(size_t n_trees, size_t leaves_per_tree, size_t *total_leaves, size_t *total_nodes) {
-    if (n_trees == 0 || leaves_per_tree == 0 || (leaves_per_tree & (leaves_per_tree - 1)))
-        return set_error(PMX_ERR_ARG, "a forest needs n_trees >= 1 and leaves_per_tree a power of two");
-    if (n_trees > (SIZE_MAX / 128) / leaves_per_tree) return set_error(PMX_ERR_ARG, "forest byte size overflows size_t");
-    *total_leaves = n_trees * leaves_per_tree;
-    *total_nodes = n_trees * (2 * leaves_per_tree - 1);
-    return PMX_OK;
-}
-
-extern "C" int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t leaves_per_tree, void *stream) {
-    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest_dev: null pointer");
-    size_t total = 0, n_nodes = 0;
-    if (int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes)) return rc;
-    return merkle_levels_dev(ctx, d_nodes, n_trees, total, 2, stream);
-}
-
-extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint64_t *nodes,
-                                      uint64_t *roots) {
-    PMX_ABI_BEGIN("pmx_merkle_2to1_forest")
-    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest: null pointer");
-    size_t total = 0, n_nodes = 0;
-    if (int rc = forest_shape(n_trees, leaves_per_tree, &total, &n_nodes)) return rc;
-    PMX_BIND(ctx);
-    return merkle_host(ctx, leaves, n_trees, total, n_nodes, 2, nodes, roots);
-    PMX_ABI_END
-}
-
-// ---- authentication paths ---------------------------------------------------------------------------------------------
-extern "C" int pmx_merkle_paths(const uint64_t *nodes, size_t n_leaves, const uint64_t *indices, size_t k, uint64_t *paths_out) {
-    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_paths: null pointer");
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
-    size_t depth = 0;
-    while (((size_t)1 << depth) < n_leaves) ++depth;
-    for (size_t i = 0; i < k; ++i) {
-        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
-        size_t idx = (size_t)indices[i], first = 0, width = n_leaves;   // first node of the current level, its width
-        for (size_t level = 0; level < depth; ++level) {
-            std::memcpy(paths_out + (i * depth + level) * 4, nodes + (first + (idx ^ 1)) * 4, 32);
-            first += width;
-            width /= 2;
-            idx >>= 1;
-        }
-    }
-    return PMX_OK;
-}
-
-// k authentication paths advance one level per launch, everything resident on the device: cur[i] starts as leaves[i];
-// per level a gather kernel lays (cur[i], sibling) out as the pair array one tree level has - left / right by bit `level`
-// of indices[i] - and the 2-to-1 compression launcher (quad kernel for k <= 32768) writes the parents back into cur.
-// d_work: [k][12] u64 of scratch (cur [k][4], then pairs [k][8]).  d_ok[i] = 1 iff cur[i] == root after `depth` levels and
-// indices[i] < 2^depth (an index with bits at or above `depth` names no leaf of this tree).
-extern "C" int pmx_merkle_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
-                                           size_t depth, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream) {
-    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_verify_paths_dev: null pointer");
-    if (ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
-    if (depth >= 64) return set_error(PMX_ERR_ARG, "depth out of range");
-    if (k == 0) return PMX_OK;
-    if (k > (size_t)0x7fffffff * 64 || (depth && k > (SIZE_MAX / 32) / depth)) return set_error(PMX_ERR_ARG, "batch too large");
-    if (!aligned16(d_leaves) || !aligned16(d_paths) || !aligned16(d_work) || !aligned16(d_root)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    uint64_t *cur = d_work, *pairs = d_work + k * 4;
-    PMX_HIP(hipMemcpyAsync(cur, d_leaves, k * 32, hipMemcpyDeviceToDevice, st));
-    for (size_t level = 0; level < depth; ++level) {
-        PMX_HIP(launch_path_pairs(cur, d_paths, d_indices, depth, level, pairs, k, st));
-        PMX_HIP(launch_compress(ctx->dev, ctx->t, pairs, cur, k, st));
-    }
-    PMX_HIP(launch_path_check(cur, d_root, d_indices, (uint64_t)1 << depth, d_ok, k, st));   // depth < 64 (checked above)
-    return PMX_OK;
-}
-
-// Host buffers: one upload of (leaves, indices, paths, root), `depth` level steps on the device, one download of ok.
-extern "C" int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths,
-                                       size_t depth, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
-    PMX_ABI_BEGIN("pmx_merkle_verify_paths")
-    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_verify_paths: null pointer");
-    if (ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
-    if (depth >= 64) return set_error(PMX_ERR_ARG, "depth out of range");
-    if (k == 0) return PMX_OK;
-    if (k > SIZE_MAX / 128 || (depth && k > (SIZE_MAX / 32) / depth)) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: leaves [k][4] | work [k][12];  slot 1: paths [k][depth][4];  slot 2: root [4] | indices [k];  slot 3: ok [k]
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, k * 128, &d0))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, k * depth * 32, &d1))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, 32 + k * 8, &d2))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, k, &d3))) return rc;
-    uint64_t *d_leaves = (uint64_t *)d0, *d_work = d_leaves + k * 4, *d_root = (uint64_t *)d2, *d_idx = d_root + 4;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d_leaves, leaves, k * 32, hipMemcpyHostToDevice, ctx->stream));
-    if (depth) PMX_HIP(hipMemcpyAsync(d1, paths, k * depth * 32, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = pmx_merkle_verify_paths_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, k, d_root, (uint8_t *)d3, d_work, ctx->stream))) return rc;
-    PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
-    PMX_ABI_END
-}
-
-// ---- trees of any arity ------------------------------------------------------------------------------------------------
-// The 2-to-1 layouts generalised (at arity 2 every array is byte for byte the one the entries above produce and accept): a parent is
-// (new; absorb(its arity children); squeeze_native(1))[0], one permutation for arity <= rate (mod.rs:126-135, 219-230, 324-328).  The
-// levels run through merkle_levels_dev / merkle_host above; only the shapes and the paths are new here.
-// depth = log_arity(n_leaves), n_nodes = n_leaves + n_leaves / arity + ... + 1; refused when n_nodes * 32 does not fit size_t.
-static int ary_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
-    if (arity < 2) return set_error(PMX_ERR_ARG, "arity must be at least 2");
-    if (n_leaves == 0) return set_error(PMX_ERR_ARG, "n_leaves must be a power of the arity");
-    size_t d = 0, nodes = 0;
-    for (size_t width = n_leaves;; width /= arity, ++d) {
-        if (width > SIZE_MAX / 32 - nodes) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-        nodes += width;
-        if (width == 1) break;
-        if (width % arity) return set_error(PMX_ERR_ARG, "n_leaves must be a power of the arity");
-    }
-    *depth = d;
-    *n_nodes = nodes;
-    return PMX_OK;
-}
-// arity^depth, the number of leaves of a tree given by its depth; refused when it does not fit 64 bits
-static int ary_leaves(uint32_t arity, size_t depth, uint64_t *out) {
-    if (arity < 2) return set_error(PMX_ERR_ARG, "arity must be at least 2");
-    uint64_t n = 1;
-    for (size_t l = 0; l < depth; ++l) {
-        if (n > UINT64_MAX / arity) return set_error(PMX_ERR_ARG, "arity^depth overflows 64 bits");
-        n *= arity;
-    }
-    *out = n;
-    return PMX_OK;
-}
-static int ary_forest_shape(size_t n_trees, size_t leaves_per_tree, uint32_t arity, size_t *total_leaves, size_t *total_nodes) {
-    size_t depth = 0, tree_nodes = 0;
-    if (int rc = ary_shape(leaves_per_tree, arity, &depth, &tree_nodes)) return rc;
-    if (n_trees == 0) return set_error(PMX_ERR_ARG, "a forest needs n_trees >= 1");
-    if (n_trees > (SIZE_MAX / 32) / tree_nodes) return set_error(PMX_ERR_ARG, "forest byte size overflows size_t");
-    *total_leaves = n_trees * leaves_per_tree;
-    *total_nodes = n_trees * tree_nodes;
-    return PMX_OK;
-}
-
-extern "C" int pmx_merkle_ary_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
-    if (!depth || !n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_shape: null pointer");
-    return ary_shape(n_leaves, arity, depth, n_nodes);
-}
-
-extern "C" int pmx_merkle_ary_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream) {
-    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_dev: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    return merkle_levels_dev(ctx, d_nodes, 1, n_leaves, arity, stream);
-}
-
-extern "C" int pmx_merkle_ary(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root) {
-    PMX_ABI_BEGIN("pmx_merkle_ary")
-    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ary: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
-    return merkle_host(ctx, leaves, 1, n_leaves, n_nodes, arity, nodes, root);
-    PMX_ABI_END
-}
-
-extern "C" int pmx_merkle_ary_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t leaves_per_tree, uint32_t arity, void *stream) {
-    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_forest_dev: null pointer");
-    size_t total = 0, n_nodes = 0;
-    if (int rc = ary_forest_shape(n_trees, leaves_per_tree, arity, &total, &n_nodes)) return rc;
-    return merkle_levels_dev(ctx, d_nodes, n_trees, total, arity, stream);
-}
-
-extern "C" int pmx_merkle_ary_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint32_t arity,
-                                     uint64_t *nodes, uint64_t *roots) {
-    PMX_ABI_BEGIN("pmx_merkle_ary_forest")
-    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_forest: null pointer");
-    size_t total = 0, n_nodes = 0;
-    if (int rc = ary_forest_shape(n_trees, leaves_per_tree, arity, &total, &n_nodes)) return rc;
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
-    return merkle_host(ctx, leaves, n_trees, total, n_nodes, arity, nodes, roots);
-    PMX_ABI_END
-}
-
-// ---- openings: per level the arity - 1 siblings in child order, the running node's own slot left out -----------------------------
-extern "C" int pmx_merkle_ary_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
-                                    uint64_t *paths_out) {
-    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_paths: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    for (size_t i = 0; i < k; ++i)     // (before anything is written)
-        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
-    const size_t sib = arity - 1;
-    for (size_t i = 0; i < k; ++i) {
-        size_t idx = (size_t)indices[i], first = 0, width = n_leaves;   // first node of the current level, its width
-        for (size_t level = 0; level < depth; ++level) {
-            const size_t digit = idx % arity, base = first + (idx - digit);
-            uint64_t *row = paths_out + (i * depth + level) * sib * 4;
-            std::memcpy(row, nodes + base * 4, digit * 32);
-            std::memcpy(row + digit * 4, nodes + (base + digit + 1) * 4, (sib - digit) * 32);
-            first += width;
-            width /= arity;
-            idx /= arity;
-        }
-    }
-    return PMX_OK;
-}
-
-// the same gather on the device: nodes, indices and paths stay where they are (an index >= n_leaves, which the host cannot see, gets
-// an all-zero path)
-extern "C" int pmx_merkle_ary_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
-                                        size_t k, uint64_t *d_paths, void *stream) {
-    if (!ctx || ((!d_nodes || !d_indices || !d_paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_paths_dev: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0 || depth == 0) return PMX_OK;
-    const size_t per = depth * (arity - 1);     // elements per path (depth <= 64, arity <= PMX_MAX_WIDTH)
-    if (k > (SIZE_MAX / 32) / per || k > ((size_t)0x7fffffff * 64) / per) return set_error(PMX_ERR_ARG, "batch too large");
-    if (!aligned16(d_nodes) || !aligned16(d_paths)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    PMX_HIP(launch_paths_gather(d_nodes, n_leaves, arity, depth, d_indices, d_paths, k, (hipStream_t)stream));
-    return PMX_OK;
-}
-
-// pmx_merkle_verify_paths_dev for any arity: per level a gather kernel lays the arity children of every path's parent out as the rows
-// one tree level has, and the compression launcher of that arity writes the parents back into cur.
-// d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).
-// (the level loop behind the entry's own checks, shared with pmx_merkle_ragged_verify_paths_dev: `limit` is what an index must stay below)
-static int ary_verify_levels_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths, size_t depth,
-                                 uint32_t arity, uint64_t limit, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream) {
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0) return PMX_OK;
-    // (depth <= 64 and arity <= PMX_MAX_WIDTH here: the products below stay small)
-    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
-        return set_error(PMX_ERR_ARG, "batch too large");
-    if (!aligned16(d_leaves) || !aligned16(d_paths) || !aligned16(d_work) || !aligned16(d_root)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    uint64_t *cur = d_work, *rows = d_work + k * 4;
-    PMX_HIP(hipMemcpyAsync(cur, d_leaves, k * 32, hipMemcpyDeviceToDevice, st));
-    uint64_t pow = 1;     // arity^level
-    for (size_t level = 0; level < depth; ++level, pow *= arity) {
-        PMX_HIP(launch_path_children(cur, d_paths, d_indices, depth, level, pow, arity, rows, k, st));
-        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
-    }
-    PMX_HIP(launch_path_check(cur, d_root, d_indices, limit, d_ok, k, st));
-    return PMX_OK;
-}
-extern "C" int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
-                                               size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
-                                               void *stream) {
-    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths_dev: null pointer");
-    uint64_t n_leaves = 0;
-    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
-    return ary_verify_levels_dev(ctx, d_leaves, d_indices, d_paths, depth, arity, n_leaves, k, d_root, d_ok, d_work, stream);
-}
-
-// Host buffers: one upload of (leaves, indices, paths, root), `depth` level steps on the device, one download of ok.
-static int ary_verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth, uint32_t arity,
-                           uint64_t limit, size_t k, const uint64_t *root, uint8_t *ok_out) {
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0) return PMX_OK;
-    if (k > (SIZE_MAX / 64) / (arity + 2) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
-        return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: leaves [k][4] | work [k][(arity + 1) * 4];  slot 1: paths [k][depth][arity - 1][4];  slot 2: root [4] | indices [k];  slot 3: ok [k]
-    const size_t path_bytes = k * depth * (arity - 1) * 32;
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, k * (arity + 2) * 32, &d0))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, path_bytes, &d1))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, 32 + k * 8, &d2))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, k, &d3))) return rc;
-    uint64_t *d_leaves = (uint64_t *)d0, *d_work = d_leaves + k * 4, *d_root = (uint64_t *)d2, *d_idx = d_root + 4;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d_leaves, leaves, k * 32, hipMemcpyHostToDevice, ctx->stream));
-    if (path_bytes) PMX_HIP(hipMemcpyAsync(d1, paths, path_bytes, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = ary_verify_levels_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, limit, k, d_root, (uint8_t *)d3, d_work, ctx->stream)))
-        return rc;
-    PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
-}
-extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
-                                           uint32_t arity, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
-    PMX_ABI_BEGIN("pmx_merkle_ary_verify_paths")
-    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths: null pointer");
-    uint64_t n_leaves = 0;
-    if (int rc = ary_leaves(arity, depth, &n_leaves)) return rc;
-    return ary_verify_host(ctx, leaves, indices, paths, depth, arity, n_leaves, k, root, ok_out);
-    PMX_ABI_END
-}
-
-// ---- leaf updates of a tree of any arity ------------------------------------------------------------------------------------------
-// k leaves of a resident tree change: only their ancestors are recomputed, level by level.  While the k updates are fewer than the W
-// parents a level has, the level is  gather (the arity children of every update's parent, out of the node array) -> one compression launch
-// of k rows -> scatter (cur[i] to the parent's node); two updates under one parent compute it twice and store the same bytes.  From the
-// first level with k >= W on, the levels are the builder's own launches: an update never costs more permutations than a rebuild.
-// d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).  Enqueue only, nothing is allocated.
-extern "C" int pmx_merkle_ary_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
-                                         const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream) {
-    if (!ctx || ((!d_nodes || !d_indices || !d_new_leaves || !d_work) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_update_dev: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (!aligned16(d_nodes) || !aligned16(d_new_leaves) || !aligned16(d_work)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0) return PMX_OK;
-    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
-    PMX_BIND(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    uint64_t *cur = d_work, *rows = d_work + k * 4;
-    PMX_HIP(launch_node_scatter(d_new_leaves, d_indices, 1, n_leaves, 0, d_nodes, k, st));
-    size_t first = 0, width = n_leaves;      // level l: its first node, its width
-    uint64_t pow = arity;                    // arity^(l+1)
-    for (size_t l = 0; l < depth; ++l, pow *= arity) {
-        const size_t parents = width / arity;
-        if (k >= parents) {     // the rest of the tree as whole levels
-            for (; width > 1; first += width, width /= arity)
-                PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_nodes + first * 4, d_nodes + (first + width) * 4, arity, width / arity, st));
-            break;
-        }
-        PMX_HIP(launch_node_children(d_nodes, d_indices, pow, n_leaves, first, arity, rows, k, st));
-        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
-        PMX_HIP(launch_node_scatter(cur, d_indices, pow, n_leaves, first + width, d_nodes, k, st));
-        first += width;
-        width = parents;
-    }
-    return PMX_OK;
-}
-
-// Host buffers.  The node array stays on the host: the plan (pmx_merkle_plan.hpp) packs the children rows of every distinct ancestor, one
-// upload takes them to the device with the slots their digests go to, each level is one compression launch and one scatter, one download
-// brings all digests back, and only then is `nodes` written.
-extern "C" int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices,
-                                     const uint64_t *new_leaves, size_t k, uint64_t *root) {
-    PMX_ABI_BEGIN("pmx_merkle_ary_update")
-    if (!ctx || !nodes || ((!indices || !new_leaves) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_update: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ary_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    const size_t bad = merkle_update_first_bad(indices, k, n_leaves);     // (before anything is written)
-    if (bad < k) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[bad]);
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    MerkleUpdatePlan plan;
-    merkle_update_plan(nodes, n_leaves, arity, indices, new_leaves, k, &plan);
-    const size_t n_rows = plan.n_rows();
-    std::vector<uint64_t> digests(n_rows * 4);
-    if (n_rows) {
-        PMX_BIND(ctx);
-        int rc = PMX_OK;
-        std::lock_guard<std::mutex> lock(ctx->host_lock);
-        // slot 0: rows [n_rows][arity][4] | slots [n_rows];  slot 1: digests [n_rows][4]
-        void *d0 = nullptr, *d1 = nullptr;
-        if ((rc = ctx_scratch(ctx, 0, plan.upload.size() * 8, &d0))) return rc;
-        if ((rc = ctx_scratch(ctx, 1, n_rows * 32, &d1))) return rc;
-        uint64_t *d_rows = (uint64_t *)d0, *d_slots = d_rows + n_rows * arity * 4, *d_dig = (uint64_t *)d1;
-        StreamDrain drain{ctx};
-        PMX_HIP(hipMemcpyAsync(d0, plan.upload.data(), plan.upload.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        for (size_t l = 1; l <= depth; ++l) {
-            const size_t r = plan.row_first[l], count = plan.level_rows(l);
-            PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_rows + r * arity * 4, d_dig + r * 4, arity, count, ctx->stream));
-            if (l < depth)
-                PMX_HIP(launch_node_scatter(d_dig + r * 4, d_slots + r, 1, plan.level_rows(l + 1) * arity, plan.row_first[l + 1] * arity, d_rows,
-                                            count, ctx->stream));
-        }
-        PMX_HIP(hipMemcpyAsync(digests.data(), d1, n_rows * 32, hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    merkle_update_apply(plan, new_leaves, digests.data(), nodes);
-    if (root) std::memcpy(root, nodes + (n_nodes - 1) * 4, 32);
-    return PMX_OK;
-    PMX_ABI_END
-}
-
-// ---- trees over any number of leaves ----------------------------------------------------------------------------------------------
-// The layouts of pmx_merkle_ary* with level l + 1 of ceil(M_l / arity) nodes: the last parent of a level that does not divide absorbs the
-// r < arity children that exist, (new; absorb(r elements); squeeze_native(1))[0] - one permutation of [0, c_0 .. c_{r-1}, 0 ..]
-// (mod.rs:126-135, 219-230, 324-328).  At n_leaves = arity^depth every level divides and every launch is the one pmx_merkle_ary* makes.
-static int ragged_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
-    if (arity < 2) return set_error(PMX_ERR_ARG, "arity must be at least 2");
-    if (n_leaves == 0) return set_error(PMX_ERR_ARG, "a tree needs at least one leaf");
-    size_t d = 0, nodes = 0;
-    for (size_t width = n_leaves;; width = width / arity + (width % arity ? 1 : 0), ++d) {
-        if (width > SIZE_MAX / 32 - nodes) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-        nodes += width;
-        if (width == 1) break;
-    }
-    *depth = d;
-    *n_nodes = nodes;
-    return PMX_OK;
-}
-// every level from the one of `width` nodes at `first` up to the root: one compression launch per level
-static int ragged_levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t first, size_t width, uint32_t arity, hipStream_t st) {
-    while (width > 1) {
-        PMX_HIP(launch_compress_level(ctx->dev, ctx->t, d_nodes + first * 4, d_nodes + (first + width) * 4, arity, width, st));
-        first += width;
-        width = width / arity + (width % arity ? 1 : 0);
-    }
-    return PMX_OK;
-}
-
-extern "C" int pmx_merkle_ragged_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
-    if (!depth || !n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_shape: null pointer");
-    return ragged_shape(n_leaves, arity, depth, n_nodes);
-}
-
-extern "C" int pmx_merkle_ragged_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream) {
-    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_dev: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (!aligned16(d_nodes)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    return ragged_levels_dev(ctx, d_nodes, 0, n_leaves, arity, (hipStream_t)stream);
-}
-
-extern "C" int pmx_merkle_ragged(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root) {
-    PMX_ABI_BEGIN("pmx_merkle_ragged")
-    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d, leaves, n_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = ragged_levels_dev(ctx, (uint64_t *)d, 0, n_leaves, arity, ctx->stream))) return rc;
-    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (root) PMX_HIP(hipMemcpyAsync(root, (uint64_t *)d + (n_nodes - 1) * 4, 32, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
-    PMX_ABI_END
-}
-
-// openings: the shape of pmx_merkle_ary_paths; a sibling at or beyond its level's width does not exist and is four zero words
-extern "C" int pmx_merkle_ragged_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
-                                       uint64_t *paths_out) {
-    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_paths: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    for (size_t i = 0; i < k; ++i)     // (before anything is written)
-        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
-    const size_t sib = arity - 1;
-    for (size_t i = 0; i < k; ++i) {
-        size_t idx = (size_t)indices[i], first = 0, width = n_leaves;   // first node of the current level, its width
-        for (size_t level = 0; level < depth; ++level) {
-            const size_t digit = idx % arity, base = idx - digit;
-            uint64_t *row = paths_out + (i * depth + level) * sib * 4;
-            for (size_t s = 0; s < sib; ++s) {
-                const size_t child = base + (s < digit ? s : s + 1);
-                if (child < width) std::memcpy(row + s * 4, nodes + (first + child) * 4, 32);
-                else std::memset(row + s * 4, 0, 32);
-            }
-            first += width;
-            width = width / arity + (width % arity ? 1 : 0);
-            idx /= arity;
-        }
-    }
-    return PMX_OK;
-}
-
-extern "C" int pmx_merkle_ragged_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
-                                           size_t k, uint64_t *d_paths, void *stream) {
-    if (!ctx || ((!d_nodes || !d_indices || !d_paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_paths_dev: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0 || depth == 0) return PMX_OK;
-    const size_t per = depth * (arity - 1);     // elements per path (depth <= 64, arity <= PMX_MAX_WIDTH)
-    if (k > (SIZE_MAX / 32) / per || k > ((size_t)0x7fffffff * 64) / per) return set_error(PMX_ERR_ARG, "batch too large");
-    if (!aligned16(d_nodes) || !aligned16(d_paths)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    PMX_BIND(ctx);
-    PMX_HIP(launch_paths_gather_ragged(d_nodes, n_leaves, arity, depth, d_indices, d_paths, k, (hipStream_t)stream));
-    return PMX_OK;
-}
-
-// The climb is pmx_merkle_ary_verify_paths*'s own - an absent sibling is the zero a short parent's rate lane holds - with the tree's
-// leaf count as the limit of the indices: the root does not bind n_leaves, so the caller states it, and depth must be its depth.
-static int ragged_verify_shape(size_t depth, uint32_t arity, size_t n_leaves) {
-    size_t d = 0, n_nodes = 0;
-    if (int rc = ragged_shape(n_leaves, arity, &d, &n_nodes)) return rc;
-    if (d != depth) return set_error(PMX_ERR_ARG, "depth %zu is not the depth %zu of a tree of arity %u over %zu leaves", depth, d, arity, n_leaves);
-    return PMX_OK;
-}
-
-extern "C" int pmx_merkle_ragged_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
-                                                  size_t depth, uint32_t arity, size_t n_leaves, size_t k, const uint64_t *d_root,
-                                                  uint8_t *d_ok, uint64_t *d_work, void *stream) {
-    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths_dev: null pointer");
-    if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
-    return ary_verify_levels_dev(ctx, d_leaves, d_indices, d_paths, depth, arity, (uint64_t)n_leaves, k, d_root, d_ok, d_work, stream);
-}
-
-extern "C" int pmx_merkle_ragged_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
-                                              uint32_t arity, size_t n_leaves, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
-    PMX_ABI_BEGIN("pmx_merkle_ragged_verify_paths")
-    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
-        return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths: null pointer");
-    if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
-    return ary_verify_host(ctx, leaves, indices, paths, depth, arity, (uint64_t)n_leaves, k, root, ok_out);
-    PMX_ABI_END
-}
-
-// pmx_merkle_ary_update_dev with the level widths as ceilings: the gather zero-fills the children a short parent does not have (the row
-// is then the full row launch_compress_ary takes), the scatter is the same - index / arity^(l+1) is the ancestor's index, floor division
-// nests - and the whole levels from the first one with k >= W on are the builder's launches.
-extern "C" int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
-                                            const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream) {
-    if (!ctx || ((!d_nodes || !d_indices || !d_new_leaves || !d_work) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_update_dev: null pointer");
-    size_t depth = 0, n_nodes = 0;
-    if (int rc = ragged_shape(n_leaves, arity, &depth, &n_nodes)) return rc;
-    if (!aligned16(d_nodes) || !aligned16(d_new_leaves) || !aligned16(d_work)) return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
-    if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0) return PMX_OK;
-    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
-    PMX_BIND(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    uint64_t *cur = d_work, *rows = d_work + k * 4;
-    PMX_HIP(launch_node_scatter(d_new_leaves, d_indices, 1, n_leaves, 0, d_nodes, k, st));
-    size_t first = 0, width = n_leaves;      // level l: its first node, its width
-    uint64_t pow = arity;                    // arity^(l+1) (below n_leaves * arity: no overflow)
-    for (size_t l = 0; l < depth; ++l, pow *= arity) {
-        const size_t parents = width / arity + (width % arity ? 1 : 0);
-        if (k >= parents) return ragged_levels_dev(ctx, d_nodes, first, width, arity, st);     // the rest of the tree as whole levels
-        PMX_HIP(launch_node_children_bounded(d_nodes, d_indices, pow, n_leaves, first, width, arity, rows, k, st));
-        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
-        PMX_HIP(launch_node_scatter(cur, d_indices, pow, n_leaves, first + width, d_nodes, k, st));
-        first += width;
-        width = parents;
-    }
-    return PMX_OK;
 }

@@ -1,7 +1,8 @@
-// Private definition of pmx_ctx and the helpers shared by pmx_api.cpp (one device) and pmx_mgpu.cpp (device groups).
+// Private definition of pmx_ctx and the helpers shared by pmx_api.cpp (one device), pmx_merkle.cpp (the trees) and pmx_mgpu.cpp (device groups).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <mutex>
 #include <string>
@@ -79,5 +80,21 @@ uint64_t grind_chunk();
 #define PMX_BIND(ctx)                                                                \
     ::pmx::DeviceGuard device_guard_((ctx)->device);                                 \
     if (device_guard_.err != hipSuccess) return ::pmx::hip_fail(device_guard_.err, "hipSetDevice")
+
+// Grow-only device staging of the host-buffer entry points: at least `bytes` bytes of ctx->scratch[slot] (the caller holds host_lock).
+int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out);
+
+// Host-buffer entry points queue asynchronous copies that read and write the CALLER's memory: whatever way they
+// leave (including an error half way through), nothing may still be in flight on the context's streams.
+struct StreamDrain {
+    pmx_ctx *ctx;
+    ~StreamDrain() {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream2);
+        (void)hipStreamSynchronize(ctx->stream3);
+    }
+};
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace pmx

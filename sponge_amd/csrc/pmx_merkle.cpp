@@ -1,0 +1,495 @@
+// Every pmx_merkle_* entry point of include/poseidon_mi355x.h: the 2-to-1 trees and forests, the trees of any arity (a power of the arity
+// leaves) and the trees over any number of leaves (pmx_merkle_ragged*), built on one set of bodies.  A parent is (new; absorb(its
+// children); squeeze_native(1))[0], one permutation for arity <= rate (mod.rs:126-135, 219-230, 324-328); the last parent of a level that
+// does not divide absorbs the children that exist.  The layout is pmx_merkle_shape.hpp's.  The three families are one thing: at arity 2
+// every array of the arity-k entries is byte for byte the one the 2-to-1 entries produce and accept, and at n_leaves = arity^depth every
+// launch of a ragged builder is the one pmx_merkle_ary* makes (launch_compress_level on a level that divides is launch_compress_ary,
+// which at arity 2 is launch_compress).  What stays per entry is its name in the null-pointer message, its shape check with its own
+// texts, and the order of its checks; the family picks between the twin gather kernels (a ragged entry launches the bounded one whatever
+// the leaf count).  The *_dev entries only enqueue on the caller's stream: no allocation, no synchronisation.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/poseidon_mi355x.h"
+#include "pmx_ctx.hpp"
+#include "pmx_internal.hpp"
+#include "pmx_launch.hpp"
+#include "pmx_merkle_plan.hpp"
+#include "pmx_merkle_shape.hpp"
+
+using namespace pmx;
+
+namespace {
+
+using E = MerkleShapeError;
+enum class Family { pairs, pair_forest, ary, ary_forest, ragged };
+
+// the message of a refused shape, in the words of the entry's family
+int shape_error(E e, Family f) {
+    switch (e) {
+    case E::ok: return PMX_OK;
+    case E::arity: return set_error(PMX_ERR_ARG, "arity must be at least 2");
+    case E::pow_overflow: return set_error(PMX_ERR_ARG, "arity^depth overflows 64 bits");
+    case E::tree_overflow:
+        if (f != Family::pair_forest) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
+        [[fallthrough]];
+    case E::forest_overflow: return set_error(PMX_ERR_ARG, "forest byte size overflows size_t");
+    case E::no_trees:
+        if (f == Family::ary_forest) return set_error(PMX_ERR_ARG, "a forest needs n_trees >= 1");
+        [[fallthrough]];
+    default: break;     // no leaves, not a power (and the 2-to-1 forest without trees)
+    }
+    if (f == Family::pairs) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two");
+    if (f == Family::pair_forest) return set_error(PMX_ERR_ARG, "a forest needs n_trees >= 1 and leaves_per_tree a power of two");
+    if (f == Family::ragged) return set_error(PMX_ERR_ARG, "a tree needs at least one leaf");
+    return set_error(PMX_ERR_ARG, "n_leaves must be a power of the arity");
+}
+int tree_shape(size_t n_leaves, uint32_t arity, Family f, MerkleShape *s) { return shape_error(merkle_shape(n_leaves, arity, f != Family::ragged, s), f); }
+int forest_shape(size_t n_trees, size_t leaves_per_tree, uint32_t arity, Family f, size_t *total_leaves, size_t *total_nodes) {
+    return shape_error(merkle_forest_shape(n_trees, leaves_per_tree, arity, f == Family::pair_forest, total_leaves, total_nodes), f);
+}
+// The root does not bind n_leaves of a ragged tree, so the caller of a verifier states it, and depth must be its depth.
+int ragged_verify_shape(size_t depth, uint32_t arity, size_t n_leaves) {
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    if (s.depth != depth) return set_error(PMX_ERR_ARG, "depth %zu is not the depth %zu of a tree of arity %u over %zu leaves", depth, s.depth, arity, n_leaves);
+    return PMX_OK;
+}
+
+// one permutation compresses at most `rate` children (absorbing more into a fresh sponge permutes in between: a hash row)
+int arity_fits(const pmx_ctx *ctx, uint32_t arity) {
+    if (arity == 2 && ctx->dev.rounds.rate < 2) return set_error(PMX_ERR_CONFIG, "2-to-1 compression needs rate >= 2");
+    if (arity > ctx->dev.rounds.rate)
+        return set_error(PMX_ERR_CONFIG, "arity %u exceeds the rate %u: more children than the rate is a hash row (pmx_hash_batch_dev), not a single compression",
+                         arity, ctx->dev.rounds.rate);
+    return PMX_OK;
+}
+int misaligned() { return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned"); }
+
+// ---- the shared bodies ------------------------------------------------------------------------------------------------------------
+// Level by level on the caller's stream, from level `lv` until the width is `stop` (1; n_trees for a forest, whose trees advance
+// together: a level of all trees is one contiguous array, and the narrowest launch is n_trees compressions wide).  (Cutting a tree into
+// subtrees on concurrent streams was measured SLOWER - 7.0 ms -> 12.5 ms at 8 streams for 2^21 leaves - because the narrow levels are
+// latency-bound, not launch-bound.)
+int levels_dev(pmx_ctx *ctx, uint64_t *d_nodes, MerkleLevel lv, size_t stop, hipStream_t st) {
+    for (; lv.width > stop; lv.advance())
+        PMX_HIP(launch_compress_level(ctx->dev, ctx->t, d_nodes + lv.first * 4, d_nodes + (lv.first + lv.width) * 4, lv.arity, lv.width, st));
+    return PMX_OK;
+}
+// every builder behind its shape check
+int build_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t total_leaves, uint32_t arity, size_t n_trees, void *stream) {
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (!aligned16(d_nodes)) return misaligned();
+    PMX_BIND(ctx);
+    return levels_dev(ctx, d_nodes, MerkleLevel{0, total_leaves, arity}, n_trees, (hipStream_t)stream);
+}
+// Host buffers (the caller has bound the device): upload the leaves, the levels, download all nodes and / or the last n_trees (the roots).
+int build_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t total_leaves, size_t n_nodes, uint32_t arity, uint64_t *nodes,
+               uint64_t *roots) {
+    int rc = PMX_OK;
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    void *d = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d, leaves, total_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = build_dev(ctx, (uint64_t *)d, total_leaves, arity, n_trees, ctx->stream))) return rc;
+    if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (roots) PMX_HIP(hipMemcpyAsync(roots, (uint64_t *)d + (n_nodes - n_trees) * 4, n_trees * 32, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+}
+
+// Openings on the host: paths_out [k][depth][arity - 1][4], per level the siblings in child order with the running node's own slot left
+// out; a sibling at or beyond its level's width does not exist and is four zero words (there is none on a tree of arity^depth leaves).
+// Every index is checked before anything is written.
+int paths_host(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices, size_t k, uint64_t *paths_out) {
+    for (size_t i = 0; i < k; ++i)
+        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
+    const size_t sib = arity - 1;
+    for (size_t i = 0; i < k; ++i) {
+        size_t idx = (size_t)indices[i];
+        MerkleLevel lv{0, n_leaves, arity};
+        for (size_t level = 0; level < depth; ++level, lv.advance(), idx /= arity) {
+            const size_t digit = idx % arity, base = idx - digit;
+            uint64_t *row = paths_out + (i * depth + level) * sib * 4;
+            for (size_t s = 0; s < sib; ++s) {
+                const size_t child = base + (s < digit ? s : s + 1);
+                if (child < lv.width) std::memcpy(row + s * 4, nodes + (lv.first + child) * 4, 32);
+                else std::memset(row + s * 4, 0, 32);
+            }
+        }
+    }
+    return PMX_OK;
+}
+// the same gather on the device: nodes, indices and paths stay where they are (an index >= n_leaves, which the host cannot see, gets
+// an all-zero path)
+int paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, size_t depth, bool ragged, const uint64_t *d_indices, size_t k,
+              uint64_t *d_paths, void *stream) {
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0 || depth == 0) return PMX_OK;
+    const size_t per = depth * (arity - 1);     // elements per path (depth <= 64, arity <= PMX_MAX_WIDTH)
+    if (k > (SIZE_MAX / 32) / per || k > ((size_t)0x7fffffff * 64) / per) return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_nodes) || !aligned16(d_paths)) return misaligned();
+    PMX_BIND(ctx);
+    PMX_HIP((ragged ? launch_paths_gather_ragged : launch_paths_gather)(d_nodes, n_leaves, arity, depth, d_indices, d_paths, k, (hipStream_t)stream));
+    return PMX_OK;
+}
+
+// k authentication paths climb one level per step, everything resident on the device: cur[i] starts as leaves[i]; per level a gather
+// kernel lays the arity children of every path's parent out as the rows one tree level has - cur[i] at digit `level` of indices[i], the
+// siblings of paths[i][level] around it (an absent sibling is the zero a short parent's rate lane holds) - and the compression launcher
+// writes the parents back into cur.  Arity 2 gathers with shifts (launch_path_pairs: paths [k][depth][1][4] is [k][depth][4]), any other
+// arity with divisions.  d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).  d_ok[i] = 1 iff cur[i] ==
+// root after `depth` levels and indices[i] < limit.  `pairs`: the bounds on k the 2-to-1 entries have always had.
+int verify_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths, size_t depth, uint32_t arity, uint64_t limit,
+               bool pairs, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream) {
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    // (depth <= 64 and arity <= PMX_MAX_WIDTH here: the products below stay small)
+    if (k > ((size_t)0x7fffffff * 64) / (pairs ? 1 : arity) || k > (SIZE_MAX / 32) / (arity + 1) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
+        return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_leaves) || !aligned16(d_paths) || !aligned16(d_work) || !aligned16(d_root)) return misaligned();
+    PMX_BIND(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *cur = d_work, *rows = d_work + k * 4;
+    PMX_HIP(hipMemcpyAsync(cur, d_leaves, k * 32, hipMemcpyDeviceToDevice, st));
+    uint64_t pow = 1;     // arity^level
+    for (size_t level = 0; level < depth; ++level, pow *= arity) {
+        if (arity == 2) PMX_HIP(launch_path_pairs(cur, d_paths, d_indices, depth, level, rows, k, st));
+        else PMX_HIP(launch_path_children(cur, d_paths, d_indices, depth, level, pow, arity, rows, k, st));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
+    }
+    PMX_HIP(launch_path_check(cur, d_root, d_indices, limit, d_ok, k, st));
+    return PMX_OK;
+}
+// Host buffers: one upload of (leaves, indices, paths, root), `depth` level steps on the device, one download of ok.
+int verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth, uint32_t arity, uint64_t limit,
+                bool pairs, size_t k, const uint64_t *root, uint8_t *ok_out) {
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    if (k > (pairs ? SIZE_MAX / 128 : (SIZE_MAX / 64) / (arity + 2)) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
+        return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    PMX_BIND(ctx);
+    int rc = PMX_OK;
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    // slot 0: leaves [k][4] | work [k][(arity + 1) * 4];  slot 1: paths [k][depth][arity - 1][4];  slot 2: root [4] | indices [k];  slot 3: ok [k]
+    const size_t path_bytes = k * depth * (arity - 1) * 32;
+    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, k * (arity + 2) * 32, &d0))) return rc;
+    if ((rc = ctx_scratch(ctx, 1, path_bytes, &d1))) return rc;
+    if ((rc = ctx_scratch(ctx, 2, 32 + k * 8, &d2))) return rc;
+    if ((rc = ctx_scratch(ctx, 3, k, &d3))) return rc;
+    uint64_t *d_leaves = (uint64_t *)d0, *d_work = d_leaves + k * 4, *d_root = (uint64_t *)d2, *d_idx = d_root + 4;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d_leaves, leaves, k * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (path_bytes) PMX_HIP(hipMemcpyAsync(d1, paths, path_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = verify_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, limit, pairs, k, d_root, (uint8_t *)d3, d_work, ctx->stream))) return rc;
+    PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+}
+
+// k leaves of a resident tree change: only their ancestors are recomputed, level by level.  While the k updates are fewer than the
+// parents a level has, the level is  gather (the arity children of every update's parent, out of the node array; the bounded twin
+// zero-fills the children a short parent does not have) -> one compression launch of k rows -> scatter (cur[i] to the parent's node:
+// index / arity^(l+1) is the ancestor's index, floor division nests); two updates under one parent compute it twice and store the same
+// bytes.  From merkle_update_switch_level on, the levels are the builder's own launches: an update never costs more permutations than a
+// rebuild.  d_work: [k][(arity + 1) * 4] u64 of scratch (cur [k][4], then rows [k][arity][4]).  Enqueue only, nothing is allocated.
+int update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, bool ragged, const uint64_t *d_indices, const uint64_t *d_new_leaves,
+               size_t k, uint64_t *d_work, void *stream) {
+    if (!aligned16(d_nodes) || !aligned16(d_new_leaves) || !aligned16(d_work)) return misaligned();
+    if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
+    PMX_BIND(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t *cur = d_work, *rows = d_work + k * 4;
+    PMX_HIP(launch_node_scatter(d_new_leaves, d_indices, 1, n_leaves, 0, d_nodes, k, st));
+    MerkleLevel lv{0, n_leaves, arity};
+    uint64_t pow = arity;                    // arity^(l+1) (below n_leaves * arity: no overflow)
+    for (size_t l = merkle_update_switch_level(n_leaves, arity, k); l > 0; --l, pow *= arity, lv.advance()) {
+        if (ragged) PMX_HIP(launch_node_children_bounded(d_nodes, d_indices, pow, n_leaves, lv.first, lv.width, arity, rows, k, st));
+        else PMX_HIP(launch_node_children(d_nodes, d_indices, pow, n_leaves, lv.first, arity, rows, k, st));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, rows, cur, arity, k, st));
+        PMX_HIP(launch_node_scatter(cur, d_indices, pow, n_leaves, lv.first + lv.width, d_nodes, k, st));
+    }
+    return levels_dev(ctx, d_nodes, lv, 1, st);     // the rest of the tree as whole levels
+}
+
+}  // namespace
+
+// ---- 2-to-1 trees and forests: n_leaves a power of two ---------------------------------------------------------------------------
+extern "C" int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, 2, Family::pairs, &s)) return rc;
+    return build_dev(ctx, d_nodes, n_leaves, 2, 1, stream);
+}
+
+extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_2to1")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, 2, Family::pairs, &s)) return rc;
+    PMX_BIND(ctx);
+    if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
+    return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, 2, nodes, root);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_2to1_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t leaves_per_tree, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest_dev: null pointer");
+    size_t total = 0, n_nodes = 0;
+    if (int rc = forest_shape(n_trees, leaves_per_tree, 2, Family::pair_forest, &total, &n_nodes)) return rc;
+    return build_dev(ctx, d_nodes, total, 2, n_trees, stream);
+}
+
+extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint64_t *nodes,
+                                      uint64_t *roots) {
+    PMX_ABI_BEGIN("pmx_merkle_2to1_forest")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest: null pointer");
+    size_t total = 0, n_nodes = 0;
+    if (int rc = forest_shape(n_trees, leaves_per_tree, 2, Family::pair_forest, &total, &n_nodes)) return rc;
+    PMX_BIND(ctx);
+    return build_host(ctx, leaves, n_trees, total, n_nodes, 2, nodes, roots);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_paths(const uint64_t *nodes, size_t n_leaves, const uint64_t *indices, size_t k, uint64_t *paths_out) {
+    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_paths: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, 2, Family::pairs, &s)) return rc;
+    return paths_host(nodes, n_leaves, 2, s.depth, indices, k, paths_out);
+}
+
+// (the 2-to-1 verifiers test the rate before the depth; 2^depth is the limit of the indices: one with bits at or above `depth` names no leaf)
+extern "C" int pmx_merkle_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                           size_t depth, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_verify_paths_dev: null pointer");
+    if (int rc = arity_fits(ctx, 2)) return rc;
+    if (depth >= 64) return set_error(PMX_ERR_ARG, "depth out of range");
+    return verify_dev(ctx, d_leaves, d_indices, d_paths, depth, 2, (uint64_t)1 << depth, true, k, d_root, d_ok, d_work, stream);
+}
+
+extern "C" int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths,
+                                       size_t depth, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
+    PMX_ABI_BEGIN("pmx_merkle_verify_paths")
+    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_verify_paths: null pointer");
+    if (int rc = arity_fits(ctx, 2)) return rc;
+    if (depth >= 64) return set_error(PMX_ERR_ARG, "depth out of range");
+    return verify_host(ctx, leaves, indices, paths, depth, 2, (uint64_t)1 << depth, true, k, root, ok_out);
+    PMX_ABI_END
+}
+
+// ---- trees of any arity: n_leaves a power of the arity --------------------------------------------------------------------------------
+extern "C" int pmx_merkle_ary_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
+    if (!depth || !n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_shape: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    *depth = s.depth, *n_nodes = s.n_nodes;
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_ary_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    return build_dev(ctx, d_nodes, n_leaves, arity, 1, stream);
+}
+
+extern "C" int pmx_merkle_ary(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_ary")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ary: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, arity, nodes, root);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_ary_forest_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_trees, size_t leaves_per_tree, uint32_t arity, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_forest_dev: null pointer");
+    size_t total = 0, n_nodes = 0;
+    if (int rc = forest_shape(n_trees, leaves_per_tree, arity, Family::ary_forest, &total, &n_nodes)) return rc;
+    return build_dev(ctx, d_nodes, total, arity, n_trees, stream);
+}
+
+extern "C" int pmx_merkle_ary_forest(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t leaves_per_tree, uint32_t arity,
+                                     uint64_t *nodes, uint64_t *roots) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_forest")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_forest: null pointer");
+    size_t total = 0, n_nodes = 0;
+    if (int rc = forest_shape(n_trees, leaves_per_tree, arity, Family::ary_forest, &total, &n_nodes)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    return build_host(ctx, leaves, n_trees, total, n_nodes, arity, nodes, roots);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_ary_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
+                                    uint64_t *paths_out) {
+    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_paths: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    return paths_host(nodes, n_leaves, arity, s.depth, indices, k, paths_out);
+}
+
+extern "C" int pmx_merkle_ary_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                        size_t k, uint64_t *d_paths, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_paths_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    return paths_dev(ctx, d_nodes, n_leaves, arity, s.depth, false, d_indices, k, d_paths, stream);
+}
+
+extern "C" int pmx_merkle_ary_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                               size_t depth, uint32_t arity, size_t k, const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work,
+                                               void *stream) {
+    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths_dev: null pointer");
+    uint64_t n_leaves = 0;
+    if (int rc = shape_error(merkle_leaves_of_depth(arity, depth, &n_leaves), Family::ary)) return rc;
+    return verify_dev(ctx, d_leaves, d_indices, d_paths, depth, arity, n_leaves, false, k, d_root, d_ok, d_work, stream);
+}
+
+extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                           uint32_t arity, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_verify_paths")
+    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths: null pointer");
+    uint64_t n_leaves = 0;
+    if (int rc = shape_error(merkle_leaves_of_depth(arity, depth, &n_leaves), Family::ary)) return rc;
+    return verify_host(ctx, leaves, indices, paths, depth, arity, n_leaves, false, k, root, ok_out);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_ary_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                         const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_new_leaves || !d_work) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_update_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    return update_dev(ctx, d_nodes, n_leaves, arity, false, d_indices, d_new_leaves, k, d_work, stream);
+}
+
+// Host buffers.  The node array stays on the host: the plan (pmx_merkle_plan.hpp) packs the children rows of every distinct ancestor, one
+// upload takes them to the device with the slots their digests go to, each level is one compression launch and one scatter, one download
+// brings all digests back, and only then is `nodes` written.
+extern "C" int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices,
+                                     const uint64_t *new_leaves, size_t k, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_ary_update")
+    if (!ctx || !nodes || ((!indices || !new_leaves) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ary_update: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
+    const size_t bad = merkle_update_first_bad(indices, k, n_leaves);     // (before anything is written)
+    if (bad < k) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[bad]);
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    MerkleUpdatePlan plan;
+    merkle_update_plan(nodes, n_leaves, arity, indices, new_leaves, k, &plan);
+    const size_t n_rows = plan.n_rows();
+    std::vector<uint64_t> digests(n_rows * 4);
+    if (n_rows) {
+        PMX_BIND(ctx);
+        int rc = PMX_OK;
+        std::lock_guard<std::mutex> lock(ctx->host_lock);
+        // slot 0: rows [n_rows][arity][4] | slots [n_rows];  slot 1: digests [n_rows][4]
+        void *d0 = nullptr, *d1 = nullptr;
+        if ((rc = ctx_scratch(ctx, 0, plan.upload.size() * 8, &d0))) return rc;
+        if ((rc = ctx_scratch(ctx, 1, n_rows * 32, &d1))) return rc;
+        uint64_t *d_rows = (uint64_t *)d0, *d_slots = d_rows + n_rows * arity * 4, *d_dig = (uint64_t *)d1;
+        StreamDrain drain{ctx};
+        PMX_HIP(hipMemcpyAsync(d0, plan.upload.data(), plan.upload.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        for (size_t l = 1; l <= s.depth; ++l) {
+            const size_t r = plan.row_first[l], count = plan.level_rows(l);
+            PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_rows + r * arity * 4, d_dig + r * 4, arity, count, ctx->stream));
+            if (l < s.depth)
+                PMX_HIP(launch_node_scatter(d_dig + r * 4, d_slots + r, 1, plan.level_rows(l + 1) * arity, plan.row_first[l + 1] * arity, d_rows,
+                                            count, ctx->stream));
+        }
+        PMX_HIP(hipMemcpyAsync(digests.data(), d1, n_rows * 32, hipMemcpyDeviceToHost, ctx->stream));
+        PMX_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    merkle_update_apply(plan, new_leaves, digests.data(), nodes);
+    if (root) std::memcpy(root, nodes + (s.n_nodes - 1) * 4, 32);
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// ---- trees over any number of leaves ----------------------------------------------------------------------------------------------
+extern "C" int pmx_merkle_ragged_shape(size_t n_leaves, uint32_t arity, size_t *depth, size_t *n_nodes) {
+    if (!depth || !n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_shape: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    *depth = s.depth, *n_nodes = s.n_nodes;
+    return PMX_OK;
+}
+
+extern "C" int pmx_merkle_ragged_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, void *stream) {
+    if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    return build_dev(ctx, d_nodes, n_leaves, arity, 1, stream);
+}
+
+extern "C" int pmx_merkle_ragged(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_ragged")
+    if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, arity, nodes, root);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_ragged_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, const uint64_t *indices, size_t k,
+                                       uint64_t *paths_out) {
+    if ((!nodes || !indices || !paths_out) && k) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_paths: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    return paths_host(nodes, n_leaves, arity, s.depth, indices, k, paths_out);
+}
+
+extern "C" int pmx_merkle_ragged_paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                           size_t k, uint64_t *d_paths, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_paths_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    return paths_dev(ctx, d_nodes, n_leaves, arity, s.depth, true, d_indices, k, d_paths, stream);
+}
+
+extern "C" int pmx_merkle_ragged_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices, const uint64_t *d_paths,
+                                                  size_t depth, uint32_t arity, size_t n_leaves, size_t k, const uint64_t *d_root,
+                                                  uint8_t *d_ok, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_leaves || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths_dev: null pointer");
+    if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
+    return verify_dev(ctx, d_leaves, d_indices, d_paths, depth, arity, (uint64_t)n_leaves, false, k, d_root, d_ok, d_work, stream);
+}
+
+extern "C" int pmx_merkle_ragged_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                                              uint32_t arity, size_t n_leaves, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
+    PMX_ABI_BEGIN("pmx_merkle_ragged_verify_paths")
+    if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
+        return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths: null pointer");
+    if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
+    return verify_host(ctx, leaves, indices, paths, depth, arity, (uint64_t)n_leaves, false, k, root, ok_out);
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
+                                            const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_nodes || !d_indices || !d_new_leaves || !d_work) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_update_dev: null pointer");
+    MerkleShape s;
+    if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
+    return update_dev(ctx, d_nodes, n_leaves, arity, true, d_indices, d_new_leaves, k, d_work, stream);
+}

@@ -2,7 +2,7 @@
 // Plain C++ with no HIP types (it compiles under -DPMX_HOSTCHECK and in the stand-alone programs of tests/merkle_plan).
 //
 // The node array is the one pmx_merkle_ary produces: leaves, then every level, root last; level l has n_leaves / arity^l nodes, the first
-// of them at first[l] = n_leaves + n_leaves / arity + ... + n_leaves / arity^(l-1).
+// of them at first[l] = n_leaves + n_leaves / arity + ... + n_leaves / arity^(l-1) (the level walk of pmx_merkle_shape.hpp).
 //
 //   S_0      = the distinct updated leaves, sorted;   S_{l+1} = distinct(S_l / arity)      (S_depth = {0}: the root)
 //   rows_l   = for every p in S_l (l >= 1), in order, its arity children out of level l - 1 of the host array - at level 1 with the new
@@ -20,6 +20,8 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "pmx_merkle_shape.hpp"
 
 namespace pmx {
 
@@ -52,11 +54,9 @@ inline void merkle_update_plan(const uint64_t *nodes, size_t n_leaves, uint32_t 
     P = MerkleUpdatePlan();
     P.arity = arity;
     P.n_leaves = n_leaves;
-    size_t at = 0;
-    for (size_t width = n_leaves;; width /= arity) {
-        P.first.push_back(at);
-        at += width;
-        if (width == 1) break;
+    for (MerkleLevel lv{0, n_leaves, arity};; lv.advance()) {
+        P.first.push_back(lv.first);
+        if (lv.width == 1) break;
     }
     P.depth = P.first.size() - 1;
     P.level.resize(P.depth + 1);

@@ -143,23 +143,9 @@ class MerkleTree:
         if out.size == 0:
             return out
         nodes = np.ascontiguousarray(self.nodes, dtype=np.uint64)
-        L, ctx, dev = _lib.lib(), self.parameters.context(self.device), self.device
-        blocks: List[ctypes.c_void_p] = []
-        try:
-            for nbytes in (nodes.nbytes, idx.nbytes, out.nbytes):
-                d = ctypes.c_void_p()
-                _lib.check(L.pmx_device_alloc(dev, ctypes.byref(d), nbytes))
-                blocks.append(d)
-            d_nodes, d_idx, d_out = blocks
-            _lib.check(L.pmx_device_upload(dev, d_nodes, ctypes.c_void_p(nodes.ctypes.data), nodes.nbytes, None))
-            _lib.check(L.pmx_device_upload(dev, d_idx, ctypes.c_void_p(idx.ctypes.data), idx.nbytes, None))
-            gather = ctx.merkle_ragged_paths_dev if self.ragged else ctx.merkle_ary_paths_dev
-            gather(d_nodes, self.n_leaves, self.arity, d_idx, idx.shape[0], d_out, None)
-            _lib.check(L.pmx_device_download(dev, ctypes.c_void_p(out.ctypes.data), d_out, out.nbytes, None))
-            _lib.check(L.pmx_stream_synchronize(dev, None))
-        finally:
-            for d in blocks:
-                L.pmx_device_free(dev, d)
+        ctx = self.parameters.context(self.device)
+        gather = ctx.merkle_ragged_paths_dev if self.ragged else ctx.merkle_ary_paths_dev
+        self._with_device_blocks([nodes, idx, out.nbytes], lambda d: gather(d[0], self.n_leaves, self.arity, d[1], idx.shape[0], d[2], None), {2: out})
         return out
 
 

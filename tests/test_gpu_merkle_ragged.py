@@ -308,6 +308,44 @@ def test_verification_at_depth_zero_compares_the_leaf_with_the_root():
         assert got.tolist() == [1, 0, 0]
 
 
+def test_arity_two_climbs_through_the_shift_gather_of_the_2to1_verifier():
+    """At arity 2 the verifiers of every family gather a level's rows with the 2-to-1 verifier's kernel (bit `level` of the index, not
+    a division).  5 leaves (levels 5, 3, 2, 1: two of them with an absent sibling), BLS12-381 t = 3: every leaf's opening, an index
+    equal to n_leaves and a path with a flipped word, host and device entry, against the oracle's climb.  Then 8 leaves through
+    pmx_merkle_ary_verify_paths* at arity 2: the verdicts of pmx_merkle_verify_paths on the same bytes."""
+    label, a, m = "t3", 2, 5
+    f, cfg, cr = M.config(label)
+    leaves, nodes = M.cached_tree(label, a, m)
+    assert M.widths(m, a) == [5, 3, 2, 1]
+    idx = np.array([0, 1, 2, 3, 4, m, 2], dtype=np.uint64)
+    real = np.minimum(idx, np.uint64(m - 1)).astype(np.int64)          # the index that names no leaf carries the last leaf's opening
+    paths, mine, root = M.open_paths(nodes, m, a, real), np.array(leaves[real]), np.array(nodes[-1])
+    assert not paths[4, 0].any() and not paths[4, 1].any() and paths[4, 2].any(), "leaf 4 has no sibling on two levels"
+    paths[6, 1, 0, 3] ^= np.uint64(1) << np.uint64(40)                  # a present sibling of leaf 2: node 0 of level 1
+    top = M.climb(cr, mine, real, paths, a, m)
+    want = [int(i < m and np.array_equal(t, root)) for i, t in zip(idx.tolist(), top)]
+    assert want == [1, 1, 1, 1, 1, 0, 0]
+    for got in _verify_both(label, a, m, mine, idx, paths, root):
+        assert got.tolist() == want
+    # a power of two: the arity-k verifier at arity 2 and the 2-to-1 verifier read the same bytes ([k][depth][1][4] is [k][depth][4])
+    m = 8
+    leaves, nodes = M.cached_tree(label, a, m)
+    idx = np.array([0, 1, 2, 3, 4, 5, 6, 7, m, 2], dtype=np.uint64)
+    real = np.minimum(idx, np.uint64(m - 1)).astype(np.int64)
+    paths, mine, root = M.open_paths(nodes, m, a, real), np.array(leaves[real]), np.array(nodes[-1])
+    paths[9, 1, 0, 3] ^= np.uint64(1) << np.uint64(40)
+    k, ctx = len(idx), _ctx(label)
+    want = S.verify_paths(cfg, mine, idx, paths.reshape(k, 3, 4), root).astype(np.uint8).tolist()
+    assert want == [1] * 8 + [0, 0]
+    assert want == [int(i < m and np.array_equal(t, root)) for i, t in zip(idx.tolist(), M.climb(cr, mine, real, paths, a, m))]
+    assert ctx.merkle_ary_verify_paths(mine, idx, paths, 3, a, root).tolist() == want
+    d = [_dev(x) for x in (mine, idx, paths, root)]
+    d_ok, d_work = _dev(np.full(k + 1, 9, dtype=np.uint8)), _dev(np.zeros(k * (a + 1) * 4, dtype=np.uint64))
+    ctx.merkle_ary_verify_paths_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 3, a, k, d[3].data_ptr(), d_ok.data_ptr() + 1,
+                                    d_work.data_ptr(), _stream())
+    assert _host(d_ok, np.uint8).tolist() == [9] + want
+
+
 # ---- updates ------------------------------------------------------------------------------------------------------------------
 def _update_case(label, a, m, k, wild):
     """(indices, new leaves, old tree with marked rows, expected array).  Distinct indices that include the last leaf - under the only
