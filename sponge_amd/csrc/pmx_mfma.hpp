@@ -18,12 +18,16 @@
 //   * lanes 32-63 of an MFMA feed the SECOND half of every k-step for the columns (states) of lanes 0-31, not states of
 //     their own.  So a k-step is two MFMAs - states 0-31 and states 32-63 of the wave - and before them each lane hands the
 //     half of its byte registers its partner lane (+-32) must feed to that partner (v_permlane32_swap, once per layer);
-//     afterwards the 32 sums of a state sit half on its own lane and half on the partner: sixteen more swaps per row;
+//     afterwards the 32 sums of a state sit half on its own lane and half on the partner: sixteen more swaps per row - eight where the
+//     row has at most 15 inputs (mfma_row_pairs below), whose sums are small enough to be folded in pairs, S_e + 256 S_{e+1} in one
+//     32-bit register, before they travel;
 //   * the 32 sums S_e (|S_e| <= 32 n_in * 128 * 128 < 2^24 for the n_in <= 17 inputs of the longest layer) are the integer
 //     V = sum_e S_e 2^(8e) + the row's correction = sum u Y < n_in * 32 * 255 * p (2^272.1 at n_in = 17, p near 2^255): eight 64-bit word
 //     sums, a carry pass with ONE Montgomery step of 24 bits inside it (the table carries the 2^24: one multiply-add per word on top of the
 //     word sum, mfma_row_acc) and a re-cut of the words into nine 29-bit limbs give the row (V + m p) / 2^24 < 2^248.1 + p < 2^256 -
-//     instead of 810 multiplies.  kMfmaMaxInputs below ties the window size and the widest state to these budgets.
+//     instead of 810 multiplies.  kMfmaMaxInputs below ties the window size and the widest state to these budgets.  A row finish is
+//     84 VALU instructions (16 swaps, 47 for the words, 2 for m, 17 for the limbs), 74 in the paired form (16 pairs, 8 swaps, 31, 2, 17):
+//     every row of n_in <= 15 inputs - all of t <= 8, the dense layers and history rows of t = 9; its window layers (17 inputs) keep 84.
 //
 // The table of one row (n_in KiB: 9 for a dense row of t = 9, 17 for a row of its window layers) is streamed by every wave for itself,
 // from global memory (L2 / L1) into a ring of registers at least six k-steps ahead of its use (matrix_rows_mfma_w below; rounds 3-5 passed
@@ -35,7 +39,7 @@
 
 namespace pmx {
 
-// Widths whose dense layers go to the matrix cores.  A row costs ~85 VALU instructions of finish plus its share of the state's
+// Widths whose dense layers go to the matrix cores.  A row costs 74 .. 84 VALU instructions of finish plus its share of the state's
 // re-cut (27 per element) and 2 t MFMA issue slots (58 clocks of the matrix pipe each), against 81 t + 81 multiplies and their carries on the VALU.
 #define PMX_MFMA_MIN_T 3
 #define PMX_MFMA_MAX_T 9   // (a row's mid-column budget and the 36 t / 32 k-steps are laid out for t <= 9)
@@ -70,6 +74,14 @@ PMX_FN constexpr int mfma_window_hist(int k) { return (k - 1) * (k - 2) / 2; }  
 constexpr int kMfmaMaxInputs = PMX_MFMA_MAX_T - 1 + (PMX_MFMA_WINDOW < PMX_MFMA_MAX_T ? PMX_MFMA_WINDOW : PMX_MFMA_MAX_T);
 static_assert(32 * kMfmaMaxInputs * 128 * 128 < (1 << 25), "a sum of byte products must stay inside the accumulator budget of mfma_row_acc");
 static_assert((unsigned long long)kMfmaMaxInputs * 32 * 255 < (1ull << kMfmaShift), "a row must stay below 2^256: n_in * 32 * 255 * p / 2^24 + p < 2 p");
+// Rows whose byte sums are folded in PAIRS in front of the lane swap (mfma_row_acc_pairs_p below): S_e + 256 S_{e+1} with |S| <= 32 n_in 2^14
+// must fit a signed 32-bit register, 257 * 32 * n_in * 2^14 < 2^31 - n_in <= 15 (2 021 130 240 at 15, 2 155 872 256 at 16): every dense
+// layer, every history row (k <= 8 inputs), the window layers of t <= 8 (2 t - 1 inputs).  The window layers of t = 9 (17 inputs) and
+// anything else above the bound keep the four-weight finish; the choice is made at compile time from the row's input count, nowhere else.
+PMX_FN constexpr bool mfma_row_pairs(int n_in) { return 257ll * 32 * n_in * (128 * 128) < (1ll << 31); }
+static_assert(mfma_row_pairs(15), "pairs of byte sums fit 32 bits up to 15 inputs");
+static_assert(!mfma_row_pairs(16), "... and no further: a row of 16 inputs or more keeps the four-weight finish");
+static_assert(mfma_row_pairs(PMX_MFMA_MAX_T) && mfma_row_pairs(PMX_MFMA_MAX_T - 1), "dense layers and history rows (at most MAX_T - 1 inputs) take the paired finish");
 // The history terms of a window's S-box inputs, x_{k+1} - z_k = u_k + sum_{i<k} h_{k,i} z_i (k = 2 .. K - 1): at t = 3 - ONE term per window -
 // a product by a shifted table on the VALU (pmx_field.hpp: tab_lanes_stream; profiles/r04/q_ab_history_tables.txt), from t = 4 rows on the matrix
 // cores (below; profiles/r05/k_ab_history_rows_on_the_matrix_cores.txt, l_ab_history_rows_t4_t5.txt: t = 4 +1.8 %, 5 +3.7 %, 6 +6.3 %, 7 +4.7 %,
@@ -174,6 +186,58 @@ PMX_FN void mfma_row_acc_p(const int32_t (&R)[8][4], const long long *corr, cons
     }
     a[8] = (uint32_t)carry;   // V + m p >= 0: the top carry is not negative
 }
+// The same from PAIRS of sums (rows of at most 15 inputs: mfma_row_pairs).  The lane that holds the sums behind the products folds
+// them two by two - one v_lshl_add_u32 - BEFORE they change lanes, so eight swaps bring a state's 32 sums home instead of sixteen, and a
+// word is  t = corr[w] + carry + Q[w][0] + Q[w][1] 2^16  (+ m p_w):  four v_mad per word (three for word 0) instead of six.
+// Q[w][h] = S_{4w + 2h} + 256 S_{4w + 2h + 1} exactly (no wrap inside the bound), so t, m, the carries and a[] are those of mfma_row_acc_p
+// bit for bit.  74 VALU instructions per row against 84.
+#if defined(PMX_HOSTCHECK) && !defined(__HIPCC__)
+// tests/hostcheck/pmx_row_finish_check.cpp: counts the pairs that do not fit a signed 32-bit register (a weak reference: the other host builds
+// of these headers, which check other things, need not define it)
+void hostcheck_pair_fits_32(long long q) __attribute__((weak));
+#endif
+PMX_FN int32_t mfma_pair_sums(int32_t lo, int32_t hi) {
+#if defined(PMX_HOSTCHECK) && !defined(__HIPCC__)
+    if (hostcheck_pair_fits_32) hostcheck_pair_fits_32((long long)lo + 256ll * (long long)hi);   // every pair of every row the host build computes
+#endif
+    return (int32_t)(((uint32_t)hi << 8) + (uint32_t)lo);
+}
+PMX_FN void mfma_row_acc_pairs_p(const int32_t (&Q)[8][2], const long long *corr, const uint32_t *p32, uint32_t pinv, uint32_t (&a)[9]) {
+    // (weights in VECTOR registers behind an opaque v_mov, as in mfma_row_acc_p and for the same reason: the correction, a scalar pair,
+    // stays the addend of the word's first mad as it stands)
+    int w1, w16;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_mov_b32 %0, 1" : "=v"(w1));
+    asm("v_mov_b32 %0, 0x10000" : "=v"(w16));
+#else
+    w1 = 1, w16 = 1 << 16;
+#endif
+    int carry = 0;
+    uint32_t m = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        long long t = corr[w] + (long long)carry * w1;
+        t += (long long)Q[w][0] * w1;
+        t += (long long)Q[w][1] * w16;
+        if (w == 0) m = ((uint32_t)t * pinv) & 0xffffffu;
+        t = (long long)((uint64_t)m * p32[w] + (uint64_t)t);
+        a[w] = (uint32_t)t;
+        carry = (int)(t >> 32);
+    }
+    a[8] = (uint32_t)carry;
+}
+// the words a[] of a row from its 32 sums R[w][r] = S_{4w + r}: the paired form where the row's input count allows it
+template <int NIN>
+PMX_FN void mfma_row_acc_for(const int32_t (&R)[8][4], const long long *corr, const uint32_t *p32, uint32_t pinv, uint32_t (&a)[9]) {
+    if constexpr (mfma_row_pairs(NIN)) {
+        int32_t Q[8][2];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) Q[w][0] = mfma_pair_sums(R[w][0], R[w][1]), Q[w][1] = mfma_pair_sums(R[w][2], R[w][3]);
+        mfma_row_acc_pairs_p(Q, corr, p32, pinv, a);
+    } else {
+        mfma_row_acc_p(R, corr, p32, pinv, a);
+    }
+}
 // 32 bits of the row from bit `bit` of a[] on (a funnel shift on the device)
 PMX_FN uint32_t mfma_row_bits(const uint32_t (&a)[9], int bit) {
     const int wi = bit / 32, sh = bit % 32;
@@ -246,7 +310,9 @@ inline Fe mfma_row_host(const uint32_t *W, const uint32_t *layer, size_t n_rows,
         }
         R[e / 4][e % 4] = (int32_t)sum;
     }
-    return as_element ? mfma_row_finish(R, corr + (size_t)i * 8, f) : mfma_row_finish_operand(R, corr + (size_t)i * 8, f);
+    uint32_t a[9];
+    mfma_row_acc_for<NQ>(R, corr + (size_t)i * 8, f.io + kIoP32, f.pinv, a);   // (NQ k-steps = NQ inputs: one k-step per element)
+    return as_element ? mfma_row_limbs(a) : mfma_row_operand(a);
 }
 // the operand form of an element (device: the second half of the words goes to the partner lane)
 inline void mfma_cut_operand(const Fe &x, uint32_t *w8) { mfma_cut_element(x, w8); }
@@ -304,6 +370,37 @@ __device__ __forceinline__ void lane32_swap(uint32_t &x, uint32_t &y) {
     const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
     x = r[0];
     y = r[1];
+}
+
+// The 32 sums of every state of the wave behind the products of a row of NIN inputs (d1: states 0-31, d2: states 32-63; register
+// v = 4 g + r of lane l holds S_{8 g + 4 (l >> 5) + r}), brought home and accumulated into the words a[] of V + m p.  Rows inside
+// mfma_row_pairs fold the sums in pairs on the lane that holds them and swap eight registers; the others swap all sixteen.
+template <int NIN>
+__device__ __forceinline__ void mfma_row_home(const mfma_v16i &d1, const mfma_v16i &d2, const long long *corr, const uint32_t *p32, uint32_t pinv,
+                                              uint32_t (&a)[9]) {
+    if constexpr (mfma_row_pairs(NIN)) {
+        int32_t Q[8][2];
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+            const int g = v / 2, h = v % 2;
+            uint32_t x = (uint32_t)mfma_pair_sums(d1[4 * g + 2 * h], d1[4 * g + 2 * h + 1]);
+            uint32_t y = (uint32_t)mfma_pair_sums(d2[4 * g + 2 * h], d2[4 * g + 2 * h + 1]);
+            lane32_swap(x, y);
+            Q[2 * g][h] = (int32_t)x;
+            Q[2 * g + 1][h] = (int32_t)y;
+        }
+        mfma_row_acc_pairs_p(Q, corr, p32, pinv, a);
+    } else {
+        int32_t R4[8][4];
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            uint32_t x = (uint32_t)d1[v], y = (uint32_t)d2[v];
+            lane32_swap(x, y);
+            R4[2 * (v / 4)][v % 4] = (int32_t)x;
+            R4[2 * (v / 4) + 1][v % 4] = (int32_t)y;
+        }
+        mfma_row_acc_p(R4, corr, p32, pinv, a);
+    }
 }
 
 // Rows [lo, hi) of the layer whose tables start at `layer` (global memory; mfma_layer_words(T) words); the other rows of s
@@ -393,17 +490,9 @@ __device__ __forceinline__ void matrix_rows_mfma_w(const uint32_t (&W)[8 * NIN],
             else a[slot] = kstep(nxt, q);
             PMX_SCHED_FENCE();
         });
-        int32_t R4[8][4];
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            uint32_t x = (uint32_t)d1[v], y = (uint32_t)d2[v];
-            lane32_swap(x, y);
-            R4[2 * (v / 4)][v % 4] = (int32_t)x;
-            R4[2 * (v / 4) + 1][v % 4] = (int32_t)y;
-        }
         Fe row;
         uint32_t acc9[9];
-        mfma_row_acc_p(R4, cw, pw, f.pinv, acc9);
+        mfma_row_home<NIN>(d1, d2, cw, pw, f.pinv, acc9);
         if (!kOperandRows || i < fe_rows) row = mfma_row_limbs(acc9);
         else row = mfma_row_operand(acc9);
         if (i + 1 < (uint32_t)T) sc.set(i, row);
@@ -455,15 +544,9 @@ struct MfmaHistRow {
     }
     template <int KK>
     __device__ __forceinline__ Fe finish(const FieldRt &f) {
-        int32_t R[8][4];
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            uint32_t x = (uint32_t)d1[v], y = (uint32_t)d2[v];
-            lane32_swap(x, y);
-            R[2 * (v / 4)][v % 4] = (int32_t)x;
-            R[2 * (v / 4) + 1][v % 4] = (int32_t)y;
-        }
-        return mfma_row_finish(R, corr, f);
+        uint32_t acc9[9];
+        mfma_row_home<KK>(d1, d2, corr, f.io + kIoP32, f.pinv, acc9);
+        return mfma_row_limbs(acc9);
     }
 };
 
