@@ -54,6 +54,9 @@ pub const PMX_OP_GRIND: c_int = 5;
 pub const PMX_MODE_ABSORBING: u32 = 0;
 pub const PMX_MODE_SQUEEZING: u32 = 1;
 
+pub const PMX_MATRIX_ROW_MAJOR: u32 = 0;   // element (i, j) at (i * row_len + j) * 4
+pub const PMX_MATRIX_COL_MAJOR: u32 = 1;   // element (i, j) at (j * n_rows + i) * 4
+
 extern "C" {
     pub fn pmx_last_error() -> *const c_char;
     pub fn pmx_ctx_create(cfg: *const pmx_config, device: c_int, out: *mut *mut pmx_ctx) -> c_int;
@@ -155,6 +158,16 @@ extern "C" {
                                               d_work: *mut u64, stream: *mut c_void) -> c_int;
     pub fn pmx_merkle_ragged_update_dev(ctx: *mut pmx_ctx, d_nodes: *mut u64, n_leaves: usize, arity: u32, d_indices: *const u64,
                                         d_new_leaves: *const u64, k: usize, d_work: *mut u64, stream: *mut c_void) -> c_int;
+    // matrix commitments: the rows of a host matrix (layout PMX_MATRIX_*) hashed where they lie - leaf_i = (new; absorb(row i);
+    // squeeze_native(1))[0] - and the tree of pmx_merkle_ragged over the digests without leaving the device; host buffers only (there is
+    // no device-resident form, no forest, no device-group form)
+    pub fn pmx_matrix_leaves(ctx: *mut pmx_ctx, matrix: *const u64, n_rows: usize, row_len: usize, layout: u32, leaves_out: *mut u64) -> c_int;
+    pub fn pmx_matrix_commit(ctx: *mut pmx_ctx, matrix: *const u64, n_rows: usize, row_len: usize, layout: u32, arity: u32, nodes: *mut u64,
+                             root: *mut u64) -> c_int;
+    pub fn pmx_matrix_rows(matrix: *const u64, n_rows: usize, row_len: usize, layout: u32, indices: *const u64, k: usize,
+                           rows_out: *mut u64) -> c_int;
+    pub fn pmx_matrix_verify_rows(ctx: *mut pmx_ctx, rows: *const u64, row_len: usize, indices: *const u64, paths: *const u64, depth: usize,
+                                  arity: u32, n_rows: usize, k: usize, root: *const u64, ok_out: *mut u8) -> c_int;
     // device memory for the *_dev entry points
     pub fn pmx_device_alloc(device: c_int, d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_device_free(device: c_int, d_ptr: *mut c_void) -> c_int;

@@ -278,6 +278,36 @@ impl<F: PrimeField> BatchPoseidon<F> {
                                                    limbs_mut(&mut roots)) });
         roots
     }
+    /// Commitment to the rows of a trace / LDE matrix (`pmx_matrix_commit`; no counterpart in the reference): `matrix` holds `n_rows`
+    /// rows of `matrix.len() / n_rows` elements, column-major (`col_major`: element (i, j) at `j * n_rows + i`, one column per
+    /// polynomial) or row-major.  Every row is hashed where it lies - `new; absorb(row); squeeze_native_field_elements(1)` - and the
+    /// digests become the leaves of the tree of `arity` over any number of rows without leaving the device.  All nodes: the digests,
+    /// then every level, root last (`pmx_merkle_ragged_shape`).  Openings are `pmx_merkle_ragged_paths` on them.  (There is no
+    /// device-resident form, no forest and no device-group form.)
+    pub fn matrix_commit(&self, matrix: &[F], n_rows: usize, col_major: bool, arity: u32) -> Vec<F> {
+        assert!(n_rows > 0 && !matrix.is_empty() && matrix.len() % n_rows == 0, "matrix is not [n_rows x row_len]");
+        let layout = if col_major { ffi::PMX_MATRIX_COL_MAJOR } else { ffi::PMX_MATRIX_ROW_MAJOR };
+        let (mut depth, mut n_nodes) = (0usize, 0usize);
+        check(unsafe { ffi::pmx_merkle_ragged_shape(n_rows, arity, &mut depth, &mut n_nodes) });
+        let mut nodes = vec![F::zero(); n_nodes];
+        check(unsafe { ffi::pmx_matrix_commit(self.ctx.0, limbs(matrix), n_rows, matrix.len() / n_rows, layout, arity, limbs_mut(&mut nodes),
+                                              core::ptr::null_mut()) });
+        nodes
+    }
+    /// `k` opened rows (`rows` = `[k][row_len]`, each row contiguous) checked at once against the root of `matrix_commit` over `n_rows`
+    /// rows: `true` where the digest of `rows[i]` hashes up to `root` along `paths[i]` (`[k][depth][arity - 1]`) and `indices[i] <
+    /// n_rows`.  The root does not bind `n_rows`, so the verifier states it.
+    pub fn matrix_verify_rows(&self, rows: &[F], indices: &[u64], paths: &[F], arity: u32, n_rows: usize, root: &F) -> Vec<bool> {
+        let k = indices.len();
+        assert!(k > 0 && rows.len() % k == 0 && rows.len() >= k, "rows is not [k][row_len]");
+        let (mut depth, mut n_nodes) = (0usize, 0usize);
+        check(unsafe { ffi::pmx_merkle_ragged_shape(n_rows, arity, &mut depth, &mut n_nodes) });
+        assert_eq!(paths.len(), k * depth * (arity as usize - 1), "paths is not [k][depth][arity - 1]");
+        let mut ok = vec![0u8; k];
+        check(unsafe { ffi::pmx_matrix_verify_rows(self.ctx.0, limbs(rows), rows.len() / k, indices.as_ptr(), limbs(paths), depth, arity, n_rows, k,
+                                                   limbs(core::slice::from_ref(root)), ok.as_mut_ptr()) });
+        ok.into_iter().map(|b| b != 0).collect()
+    }
     /// 2-to-1 tree over `leaves` (power of two): all nodes, leaves first, root last.
     pub fn merkle(&self, leaves: &[F]) -> Vec<F> {
         let mut nodes = vec![F::zero(); 2 * leaves.len() - 1];

@@ -482,6 +482,51 @@ int pmx_merkle_ragged_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, c
 int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
                                  const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream);
 
+/* ---- matrix commitments: the rows of a trace / LDE matrix as the leaves of a tree ---------------------
+ * A prover holds a matrix of n_rows rows and row_len columns, almost always column-major (one column per polynomial), and commits to
+ * its ROWS: leaf_i = (new; absorb(row i); squeeze_native(1))[0], the reference sponge's own answer for a row of any length - absorb
+ * permutes whenever the rate is full and more input remains, the squeeze permutes once more (src/poseidon/mod.rs:121-150, 219-254,
+ * 321-341) -, then the tree of pmx_merkle_ragged over the n_rows digests.  (No counterpart in the reference, which has no tree.)
+ * matrix: [n_rows * row_len][4] host memory in one of the two layouts below; it is read where it lies, never transposed on the host.
+ * Bytes: leaves_out is byte for byte pmx_hash_batch(the row-major copy of the matrix, in_len = row_len, out_len = 1); nodes / root are
+ *   byte for byte pmx_merkle_ragged over those leaves ([n_nodes][4] and depth as pmx_merkle_ragged_shape(n_rows, arity) says; what the
+ *   root does not bind is said there, and a row digest binds row_len no more than a sponge binds the length of what it absorbed:
+ *   a row and the same row followed by zeros up to the next multiple of the rate have one digest); openings are
+ *   pmx_merkle_ragged_paths on `nodes`, unchanged.  row_len may be any length >= 1 - rows longer than the rate are the point.
+ * pmx_matrix_leaves: the digests alone.  pmx_matrix_commit: the digests land in the first n_rows rows of the device node array, the tree
+ *   walk of pmx_merkle_ragged_dev follows on the same stream without the leaves leaving the device, one download brings back nodes
+ *   and / or root (each may be NULL).
+ * The link: the matrix goes up in slabs of rows of at most PMX_MATRIX_SLAB_BYTES each (65536 rows at least), through two slab buffers of the context - slab
+ *   s + 1 is uploaded while slab s is hashed.  A column-major slab of rows [a, b) is one 2-D copy (b - a) * 32 bytes wide, row_len high,
+ *   source pitch n_rows * 32, into a packed column-major buffer of leading dimension b - a; a row-major slab is one contiguous copy.
+ *   One strided hash launch per slab (the units of a wave read consecutive elements of a column-major slab), on the engine
+ *   pmx_ctx_engine_info(ctx, PMX_OP_HASH, b - a, row_len) names.  A page-locked matrix (pmx_host_alloc, hipHostRegister) is copied
+ *   asynchronously from where it lies; a pageable one of at most 64 KiB goes through the context's page-locked staging block, one of
+ *   16 MiB or more is page-locked for the length of the call, and what lies between takes the runtime's pageable staging.
+ * pmx_matrix_rows: the k opened rows, a host-only gather: rows_out [k][row_len][4], each row contiguous (row-major) whatever the
+ *   layout.  Every index is checked before anything is written (an index >= n_rows is PMX_ERR_ARG naming it).
+ * pmx_matrix_verify_rows: ok[i] = 1 iff the digest of rows[i] ([k][row_len][4], as pmx_matrix_rows gives them) climbs paths[i] to
+ *   `root` AND indices[i] < n_rows: one strided hash launch over the k rows, then the climb of pmx_merkle_ragged_verify_paths (paths
+ *   [k][depth][arity - 1][4]; depth must be the depth of (n_rows, arity)).  k = 0: PMX_OK, nothing launched.
+ * Like every host-buffer entry these serialise on the context's lock and run inside the catch-all.
+ * What the family lacks: there is no device-resident form (no *_dev entry: a matrix that already lives on the device is hashed with
+ *   pmx_hash_batch_dev, row-major only), no forest of matrices and no device-group form.
+ * Errors, nothing launched or written on any: PMX_ERR_ARG for null pointers, n_rows = 0, row_len = 0, a layout that is neither of the
+ *   two, byte sizes that overflow size_t, arity < 2, a depth that is not the tree's; PMX_ERR_CONFIG for arity > rate. */
+#define PMX_MATRIX_ROW_MAJOR 0u   /* element (i, j) at matrix[(i * row_len + j) * 4] */
+#define PMX_MATRIX_COL_MAJOR 1u   /* element (i, j) at matrix[(j * n_rows  + i) * 4] */
+/* device memory of one upload slab (there are two), chosen from the sweep of profiles/matrix_commit/README.md: the smallest power of two
+ * within 1 % of the best whole-call time for rows of 8 elements.  A slab never has fewer than 65536 rows (fewer leave the chip partly
+ * empty whatever their bytes): rows longer than 16 elements take slabs of 65536 rows, 2 MiB per element of the row. */
+#define PMX_MATRIX_SLAB_BYTES ((size_t)32 << 20)
+int pmx_matrix_leaves(pmx_ctx *ctx, const uint64_t *matrix, size_t n_rows, size_t row_len, uint32_t layout, uint64_t *leaves_out);
+int pmx_matrix_commit(pmx_ctx *ctx, const uint64_t *matrix, size_t n_rows, size_t row_len, uint32_t layout, uint32_t arity,
+                      uint64_t *nodes /* may be NULL */, uint64_t *root /* may be NULL */);
+int pmx_matrix_rows(const uint64_t *matrix, size_t n_rows, size_t row_len, uint32_t layout, const uint64_t *indices, size_t k,
+                    uint64_t *rows_out);
+int pmx_matrix_verify_rows(pmx_ctx *ctx, const uint64_t *rows, size_t row_len, const uint64_t *indices, const uint64_t *paths, size_t depth,
+                           uint32_t arity, size_t n_rows, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out);
+
 /* ---- device groups: the batch sharded over the GPUs of one node -------------------------------------
  * The reference is single-threaded and has no distributed code; nothing in src/poseidon/mod.rs:62-183 couples one
  * sponge state to another, so n states are cut into `world` contiguous shards (pmx_shard_bounds), one per GPU, and

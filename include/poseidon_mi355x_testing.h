@@ -1,5 +1,5 @@
 /*
- * poseidon_mi355x_testing.h -- test hooks: of the device-group code (pmx_mgpu.cpp) and of the grinding search's chunk size (pmx_hooks.cpp).  NOT part of the product ABI (poseidon_mi355x.h),
+ * poseidon_mi355x_testing.h -- test hooks: of the device-group code (pmx_mgpu.cpp) of the grinding search's chunk size and of the matrix entries (pmx_hooks.cpp).  NOT part of the product ABI (poseidon_mi355x.h),
  * not in the Rust binding; the reference has no counterpart (it has no multi-device code at all,
  * src/poseidon/mod.rs:62-183).
  *
@@ -11,6 +11,8 @@
  */
 #ifndef POSEIDON_MI355X_TESTING_H
 #define POSEIDON_MI355X_TESTING_H
+
+#include "poseidon_mi355x.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -34,6 +36,20 @@ int pmx_mgpu_test_shared_device(int allow);
  * again).  For the test that needs a first hit in the THIRD chunk with an oracle leg of a few thousand permutations, and for the chunk
  * sweep of tools/grind_rate.py, which takes every size through the product's own host loop. */
 int pmx_test_grind_chunk(uint64_t candidates);
+
+/* pmx_matrix_leaves / pmx_matrix_commit upload their matrix in slabs of `rows` rows instead of what PMX_MATRIX_SLAB_BYTES holds (0: the
+ * product's again), so that a matrix of a few hundred rows takes the multi-slab path - two buffers, the waits between the upload and
+ * the compute stream, a short last slab - and the slab sweep of tools/matrix_commit_rate.py runs every size through the product's own
+ * host loop. */
+int pmx_test_matrix_slab_rows(uint64_t rows);
+
+/* The strided hash kernel of the matrix entries on the caller's own device buffers: d_leaves [n_rows][4] receives
+ * (new; absorb(row i); squeeze_native(1))[0] of the rows whose element k is at d_matrix + (i * row_stride + k * elem_stride) * 4 -
+ * (row_len, 1) for a row-major matrix, (1, ld) for a column-major one of leading dimension ld.  It only enqueues on `stream`; both
+ * pointers 16-byte aligned.  The product has no device-resident matrix entry; this one exists so that the kernel's memory footprint can be
+ * laid into a guard-band arena (tests/arena.py) and its time taken between events. */
+int pmx_test_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
+                               uint64_t *d_leaves, void *stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,9 @@ MAX_LOCAL_DEVICES = 16
 MODE_ABSORBING = 0
 MODE_SQUEEZING = 1
 
+MATRIX_ROW_MAJOR = 0
+MATRIX_COL_MAJOR = 1
+
 
 class PmxError(RuntimeError):
     def __init__(self, code: int, message: str):
@@ -164,6 +167,12 @@ SIGNATURES = {
     "pmx_merkle_ragged_verify_paths_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, ctypes.c_uint32, _sz, _sz, _u64p,
                                                           ctypes.c_void_p, _u64p, ctypes.c_void_p]),
     "pmx_merkle_ragged_update_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _u64p, _sz, _u64p, ctypes.c_void_p]),
+    # matrix commitments (layout, arity: uint32_t)
+    "pmx_matrix_leaves": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, ctypes.c_uint32, _u64p]),
+    "pmx_matrix_commit": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p]),
+    "pmx_matrix_rows": (ctypes.c_int, [_u64p, _sz, _sz, ctypes.c_uint32, _u64p, _sz, _u64p]),
+    "pmx_matrix_verify_rows": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _u64p, _u64p, _sz, ctypes.c_uint32, _sz, _sz, _u64p,
+                                              ctypes.c_void_p]),
     # device groups
     "pmx_shard_bounds": (ctypes.c_int, [_sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "pmx_mgpu_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
@@ -200,6 +209,8 @@ TEST_HOOK_SIGNATURES = {
     "pmx_mgpu_test_fault": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "pmx_mgpu_test_shared_device": (ctypes.c_int, [ctypes.c_int]),
     "pmx_test_grind_chunk": (ctypes.c_int, [ctypes.c_uint64]),
+    "pmx_test_matrix_slab_rows": (ctypes.c_int, [ctypes.c_uint64]),
+    "pmx_test_matrix_leaves_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _sz, _sz, _u64p, ctypes.c_void_p]),
 }
 
 _lib = None

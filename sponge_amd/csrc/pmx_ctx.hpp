@@ -76,6 +76,10 @@ struct DeviceGuard {
 // replace it, so that a test can put a hit into the third chunk without an oracle leg of two product chunks, and the chunk sweep can
 // take every size through the product's own host loop.
 uint64_t grind_chunk();
+// Rows per upload slab of the matrix entries (pmx_api.cpp), the same way: 0 in the shipped library - the slab is then what
+// PMX_MATRIX_SLAB_BYTES of device memory holds (pmx_matrix_shape.hpp: matrix_slab_rows) - or what pmx_test_matrix_slab_rows set, so that
+// a matrix of a few hundred rows takes the multi-slab path and the slab sweep runs every size through the product's own host loop.
+uint64_t matrix_slab_rows_hook();
 
 #define PMX_BIND(ctx)                                                                \
     ::pmx::DeviceGuard device_guard_((ctx)->device);                                 \

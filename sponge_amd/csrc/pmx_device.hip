@@ -745,6 +745,74 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
     }
 }
 
+// The same rows out of a matrix (pmx_matrix_*; pmx_matrix_shape.hpp has the strides of a layout): element k of row gid is at
+// in + (gid * row_stride + k * elem_stride) * 4.  Row-major rows are (row_len, 1), hash_kernel's own addressing; a column-major matrix
+// of leading dimension ld is (1, ld), where the units of a wave read consecutive elements - 2 KB in one piece per absorbed element.
+// hash_kernel's state machine word for word: ONE loop around ONE permutation call site, want_hi, fresh, an inactive lane loads nothing,
+// and every lane of a unit loads the element while the lane that owns its state element keeps it.  The input cursor is a pointer that
+// advances by the element stride, so the absorb path holds no multiplication.  A twin and not a parameter of hash_kernel: the kernel
+// behind pmx_hash_batch[_dev] stays the code it was.
+template <class Engine>
+__global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
+    hash_strided_kernel(const DevConfig d, const uint32_t *__restrict__ consts, const uint64_t *__restrict__ in, size_t in_len, size_t row_stride,
+                        size_t elem_stride, uint64_t *__restrict__ out, size_t out_len, size_t n) {
+    Engine e(d, consts);
+    const Rounds &c = e.c;
+    const size_t gid = Engine::unit();
+    const bool active = gid < n;
+    e.zero();                                                  // CryptographicSponge::new, mod.rs:219-230
+    const uint64_t *next_in = in + (active ? gid : 0) * row_stride * 4;   // element k_in of this unit's row
+    uint64_t *row_out = out + (active ? gid : 0) * out_len * 4;
+    size_t k_in = 0, rem = out_len, pos = 0;
+    uint32_t idx = 0;
+    bool squeezing = false, need = false;
+    bool fresh = c.capacity >= 1;   // (see hash_kernel)
+    const uint32_t t_all = c.rate + c.capacity;
+    uint32_t want_hi = t_all;
+    for (;;) {
+        if (need) {
+            e.permute(want_hi < t_all ? c.capacity : 0, want_hi, fresh);
+            need = false;
+            fresh = false;
+        }
+        if (k_in < in_len) {                                   // absorb_internal, mod.rs:121-150
+            if (idx == c.rate) {                               // rate full and more input remains
+                need = true;
+                idx = 0;
+                continue;
+            }
+            Fe x = fe_zero();
+            if (active) x = e.from_abi(abi_load(reinterpret_cast<const uint32_t *>(next_in)));
+            const uint32_t at = c.capacity + idx;
+            if (e.owns(at)) e.set(at, fe_normalize(fe_add_lazy(e.get(at), x)));
+            ++idx;
+            ++k_in;
+            next_in += elem_stride * 4;
+            continue;
+        }
+        if (!squeezing) {                                      // Absorbing -> permute, squeeze from 0 (mod.rs:324-328)
+            squeezing = true;
+            need = true;
+            idx = 0;
+            if (rem <= c.rate) want_hi = c.capacity + (uint32_t)rem;
+            continue;
+        }
+        const bool last = idx + rem <= c.rate;                 // squeeze_internal, mod.rs:153-182
+        const uint32_t take = last ? (uint32_t)rem : c.rate - idx;
+        for (uint32_t k = 0; k < take; ++k) {
+            const uint32_t i = c.capacity + idx + k;
+            const Abi v = e.to_abi(e.get(i));
+            if (active && e.owns(i)) abi_store(reinterpret_cast<uint32_t *>(row_out + 4 * (pos + k)), v);
+        }
+        if (last) break;
+        need = rem != c.rate;                                  // mod.rs:175, tested before the slice is advanced
+        rem -= take;
+        pos += take;
+        idx = 0;
+        if (need && rem <= c.rate) want_hi = c.capacity + (uint32_t)rem;
+    }
+}
+
 // 2-to-1 compression, the Merkle-tree primitive:  out = (new; absorb([l, r]); squeeze_native(1))[0]
 //   = permute(state with state[capacity] = l, state[capacity+1] = r, rest 0)[capacity]      (rate >= 2),
 // because absorbing rate-many-or-fewer elements into a fresh sponge permutes exactly once, at the squeeze
@@ -1109,6 +1177,13 @@ struct Launch {
                            c.consts, in, in_len, out, out_len, n);
         return hipGetLastError();
     }
+    static hipError_t hash_strided(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, size_t row_stride, size_t elem_stride,
+                                   uint64_t *out, size_t out_len, size_t n, hipStream_t st) {
+        allow_lds(hash_strided_kernel<Engine>, Engine::lds_bytes(c, t));
+        hipLaunchKernelGGL(hash_strided_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
+                           c.consts, in, in_len, row_stride, elem_stride, out, out_len, n);
+        return hipGetLastError();
+    }
     static hipError_t compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
         allow_lds(compress_kernel<Engine>, Engine::lds_bytes(c, t));
         hipLaunchKernelGGL(compress_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
@@ -1229,7 +1304,7 @@ struct Launch {
 template <class Engine>
 static const EngineOps &engine_ops() {
     using L = Launch<Engine>;
-    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::compress, &L::compress_ary, &L::compress_ary_bounded, &L::grind, &L::absorb, &L::absorb_varlen, &L::squeeze,
+    static constexpr EngineOps ops = {&L::permute, &L::hash, &L::hash_strided, &L::compress, &L::compress_ary, &L::compress_ary_bounded, &L::grind, &L::absorb, &L::absorb_varlen, &L::squeeze,
                                       &Engine::lds_bytes, &L::describe};
     return ops;
 }
@@ -1254,6 +1329,12 @@ template __global__ void permute_kernel<PMX_ONE_ENGINE>(const DevConfig, const u
 #ifdef PMX_ONE_GRIND    // (make asm1 ... EXTRA=-DPMX_ONE_GRIND: the grind kernel of the same engine as well)
 template __global__ void grind_kernel<PMX_ONE_ENGINE>(const DevConfig, const uint32_t *__restrict__, const uint64_t *__restrict__, uint32_t, uint32_t,
                                                                                 uint64_t, size_t, uint64_t *__restrict__);
+#endif
+#ifdef PMX_ONE_MATRIX   // (make asm1 ... EXTRA=-DPMX_ONE_MATRIX: the hash kernel of the same engine and its strided twin as well)
+template __global__ void hash_kernel<PMX_ONE_ENGINE>(const DevConfig, const uint32_t *__restrict__, const uint64_t *__restrict__, size_t, uint64_t *__restrict__,
+                                                                               size_t, size_t);
+template __global__ void hash_strided_kernel<PMX_ONE_ENGINE>(const DevConfig, const uint32_t *__restrict__, const uint64_t *__restrict__, size_t, size_t, size_t,
+                                                                                       uint64_t *__restrict__, size_t, size_t);
 #endif
 #ifdef PMX_ONE_RAGGED   // (make asm1 ... EXTRA=-DPMX_ONE_RAGGED: the two ragged pass kernels of the same engine as well)
 hipError_t one_ragged(const DevConfig &c, uint64_t *s, uint32_t *tg, uint32_t *ix, uint64_t *io, const uint64_t *o, size_t n, const PassScratch &p) {
@@ -1352,6 +1433,11 @@ hipError_t launch_permute(const DevConfig &c, uint32_t t, uint64_t *states, size
 hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len,
                        size_t n, hipStream_t st) {
     return select_engine(c, t, PMX_OP_HASH, n)->hash(c, t, in, in_len, out, out_len, n, st);
+}
+// the rows of a matrix (hash_strided_kernel): a hash like any other to the engine choice
+hipError_t launch_hash_strided(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, size_t row_stride, size_t elem_stride,
+                               uint64_t *out, size_t out_len, size_t n, hipStream_t st) {
+    return select_engine(c, t, PMX_OP_HASH, n)->hash_strided(c, t, in, in_len, row_stride, elem_stride, out, out_len, n, st);
 }
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
     return select_engine(c, t, PMX_OP_COMPRESS, n)->compress(c, t, in, out, n, st);

@@ -1,4 +1,4 @@
-// Host constants of the single-device entries that the test build can replace (include/poseidon_mi355x_testing.h).  Compiled twice
+// Host constants of the single-device entries that the test build can replace, and the test build's door to the strided hash kernel (include/poseidon_mi355x_testing.h).  Compiled twice
 // (Makefile): build/pmx_hooks.o for libposeidon_mi355x.so - the constants and nothing else, no hook symbol, no state - and
 // build/pmx_hooks_test.o (-DPMX_TEST_HOOKS) for libposeidon_mi355x_test.so.  (The hooks of the device-group code live in pmx_mgpu.cpp.)
 #include <atomic>
@@ -6,6 +6,7 @@
 
 #include "../../include/poseidon_mi355x.h"
 #include "pmx_ctx.hpp"
+#include "pmx_launch.hpp"
 
 namespace pmx {
 // Candidates per launch of pmx_sponge_grind (pmx_api.cpp), chosen from the sweep of profiles/grind/README.md.
@@ -22,6 +23,23 @@ uint64_t pmx::grind_chunk() {
     const uint64_t set = g_grind_chunk.load();
     return set ? set : kGrindChunk;
 }
+static std::atomic<uint64_t> g_matrix_slab_rows{0};   // 0: the product's (PMX_MATRIX_SLAB_BYTES)
+extern "C" int pmx_test_matrix_slab_rows(uint64_t rows) {
+    g_matrix_slab_rows.store(rows);
+    return PMX_OK;
+}
+uint64_t pmx::matrix_slab_rows_hook() { return g_matrix_slab_rows.load(); }
+// the strided hash kernel of the matrix entries on the caller's own device buffers and stream, out_len = 1: enqueue only
+extern "C" int pmx_test_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
+                                          uint64_t *d_leaves, void *stream) {
+    if (!ctx || !d_matrix || !d_leaves) return pmx::set_error(PMX_ERR_ARG, "pmx_test_matrix_leaves_dev: null pointer");
+    if (n_rows == 0 || row_len == 0 || n_rows > (size_t)0x7fffffff * 64) return pmx::set_error(PMX_ERR_ARG, "pmx_test_matrix_leaves_dev: bad shape");
+    if (!pmx::aligned16(d_matrix) || !pmx::aligned16(d_leaves)) return pmx::set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
+    PMX_BIND(ctx);
+    PMX_HIP(pmx::launch_hash_strided(ctx->dev, ctx->t, d_matrix, row_len, row_stride, elem_stride, d_leaves, 1, n_rows, (hipStream_t)stream));
+    return PMX_OK;
+}
 #else
 uint64_t pmx::grind_chunk() { return kGrindChunk; }
+uint64_t pmx::matrix_slab_rows_hook() { return 0; }
 #endif

@@ -14,6 +14,10 @@ hipError_t describe_launch(const DevConfig &c, uint32_t t, int op, size_t n, siz
 hipError_t launch_permute(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st);
 hipError_t launch_hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len,
                        size_t n, hipStream_t st);
+// the same rows addressed through two strides in elements (pmx_matrix_*, pmx_matrix_shape.hpp): element k of row i at
+// in + (i * row_stride + k * elem_stride) * 4; out [n][out_len][4] packed as above.  Nothing but those n * in_len elements is read.
+hipError_t launch_hash_strided(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, size_t row_stride, size_t elem_stride,
+                               uint64_t *out, size_t out_len, size_t n, hipStream_t st);
 // out[i] = 2-to-1 compression of in[2i], in[2i+1]   (rate >= 2)
 hipError_t launch_compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
 // out[i] = arity-to-1 compression of in[arity i .. arity i + arity)   (2 <= arity <= rate; arity 2 is launch_compress)
@@ -66,6 +70,8 @@ struct EngineOps {
     hipError_t (*permute)(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st);
     hipError_t (*hash)(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, size_t n,
                        hipStream_t st);
+    hipError_t (*hash_strided)(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, size_t row_stride, size_t elem_stride,
+                               uint64_t *out, size_t out_len, size_t n, hipStream_t st);
     hipError_t (*compress)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st);
     hipError_t (*compress_ary)(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st);
     // (the level with a short last row: n = ceil(n_children / arity) parents, children bounded by n_children)

@@ -443,4 +443,36 @@ private:
     int device_;
 };
 
+// Commitment to the rows of a trace / LDE matrix (pmx_matrix_commit; no counterpart in the reference): `matrix` holds n_rows rows of
+// matrix.size() / n_rows elements, column-major (element (i, j) at j * n_rows + i, one column per polynomial) or row-major.  Every row
+// is hashed where it lies - new; absorb(row); squeeze_native_field_elements(1) - and the digests are the leaves of the tree of `arity`
+// over any number of rows, without leaving the device.  All nodes: the digests, then every level, root last (pmx_merkle_ragged_shape);
+// openings are pmx_merkle_ragged_paths on them.  There is no device-resident form, no forest and no device-group form.
+inline std::vector<Fp> matrix_commit(const PoseidonConfig &parameters, const std::vector<Fp> &matrix, size_t n_rows, bool col_major = true,
+                                     uint32_t arity = 2, int device = 0) {
+    static_assert(sizeof(Fp) == 32, "a field element is four limbs");
+    size_t depth = 0, n_nodes = 0;
+    check(pmx_merkle_ragged_shape(n_rows, arity, &depth, &n_nodes));
+    if (matrix.empty() || matrix.size() % n_rows) throw std::invalid_argument("matrix is not [n_rows x row_len]");
+    std::vector<Fp> nodes(n_nodes);
+    check(pmx_matrix_commit(parameters.context(device)->get(), matrix[0].l.data(), n_rows, matrix.size() / n_rows,
+                            col_major ? PMX_MATRIX_COL_MAJOR : PMX_MATRIX_ROW_MAJOR, arity, nodes[0].l.data(), nullptr));
+    return nodes;
+}
+// k opened rows (rows = [k][row_len], each row contiguous, as pmx_matrix_rows gives them) against the root of matrix_commit over n_rows
+// rows: true where the digest of rows[i] climbs paths[i] ([k][depth][arity - 1]) to the root and indices[i] < n_rows.  The root does not
+// bind n_rows, so the verifier states it.
+inline std::vector<bool> matrix_verify_rows(const PoseidonConfig &parameters, const std::vector<Fp> &rows, const std::vector<uint64_t> &indices,
+                                            const std::vector<Fp> &paths, const Fp &root, size_t n_rows, uint32_t arity = 2, int device = 0) {
+    const size_t k = indices.size();
+    if (k == 0) return {};
+    size_t depth = 0, n_nodes = 0;
+    check(pmx_merkle_ragged_shape(n_rows, arity, &depth, &n_nodes));
+    if (rows.empty() || rows.size() % k || paths.size() != k * depth * (arity - 1)) throw std::invalid_argument("rows are [k][row_len], paths [k][depth][arity - 1]");
+    std::vector<uint8_t> ok(k);
+    check(pmx_matrix_verify_rows(parameters.context(device)->get(), rows[0].l.data(), rows.size() / k, indices.data(), paths.empty() ? nullptr : paths[0].l.data(),
+                                 depth, arity, n_rows, k, root.l.data(), ok.data()));
+    return std::vector<bool>(ok.begin(), ok.end());
+}
+
 }  // namespace pmx_host

@@ -14,7 +14,7 @@ import numpy as np
 import ctypes
 
 from . import _lib
-from .poseidon import PoseidonConfig, merkle_ragged_shape
+from .poseidon import PoseidonConfig, matrix_rows, merkle_ragged_shape
 
 
 class MerkleTree:
@@ -176,3 +176,54 @@ def verify_paths(parameters: PoseidonConfig, leaves: np.ndarray, indices, paths:
                                                   ctypes.c_void_p(paths.ctypes.data) if paths.size else None, depth, k,
                                                   ctypes.c_void_p(root.ctypes.data), ctypes.c_void_p(ok.ctypes.data)))
     return ok.astype(bool)
+
+
+LAYOUTS = {"row": _lib.MATRIX_ROW_MAJOR, "col": _lib.MATRIX_COL_MAJOR}
+
+
+class MatrixCommitment:
+    """The commitment a STARK / FRI prover makes to a trace or LDE matrix: every ROW is hashed to a digest, leaf_i = (new; absorb(row i);
+    squeeze_native(1))[0], and the digests are the leaves of a tree of `arity` over any number of rows (pmx_matrix_commit: the matrix
+    goes up in slabs, is hashed where it lies and the leaves never leave the device).
+
+    matrix is the array as it lies in memory: layout "col" (one column per polynomial, the usual one) [row_len][n_rows][4], layout "row"
+    [n_rows][row_len][4].  Nothing is transposed.  `.tree` is the MerkleTree over the digests (its nodes are those of the call),
+    `.root` its root, `.open(indices)` the opened rows - row-major, [k][row_len][4] - with their authentication paths."""
+
+    def __init__(self, parameters: PoseidonConfig, matrix: np.ndarray, layout: str = "col", arity: int = 2, device: int = 0):
+        assert layout in LAYOUTS, "layout is 'col' or 'row'"
+        matrix = np.ascontiguousarray(matrix, dtype=np.uint64)
+        assert matrix.ndim == 3 and matrix.shape[2] == 4, "a matrix is [row_len][n_rows][4] ('col') or [n_rows][row_len][4] ('row')"
+        self.layout = LAYOUTS[layout]
+        self.row_len, self.n_rows = matrix.shape[:2] if layout == "col" else matrix.shape[1::-1]
+        self.matrix, self.parameters, self.device, self.arity = matrix, parameters, device, arity
+        nodes, root = parameters.context(device).matrix_commit(matrix, self.n_rows, self.row_len, self.layout, arity)
+        self.tree = MerkleTree.__new__(MerkleTree)          # the tree of the digests, from the nodes this call brought back
+        self.tree.parameters, self.tree.device, self.tree.arity, self.tree.n_leaves = parameters, device, arity, self.n_rows
+        self.tree.depth, _ = merkle_ragged_shape(self.n_rows, arity)
+        self.tree.ragged = self.n_rows != arity ** self.tree.depth
+        self.tree.nodes, self.tree._root = nodes, root
+
+    @property
+    def root(self) -> np.ndarray:
+        return self.tree.root
+
+    def open(self, indices):
+        """(rows [k][row_len][4], paths): the opened rows (pmx_matrix_rows) and the paths of their digests (MerkleTree.paths)"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        return matrix_rows(self.matrix, self.n_rows, self.row_len, self.layout, idx), self.tree.paths(idx)
+
+
+def verify_rows(parameters: PoseidonConfig, rows: np.ndarray, indices, paths: np.ndarray, root: np.ndarray, n_rows: int, arity: int = 2,
+                device: int = 0) -> np.ndarray:
+    """k opened rows [k][row_len][4] against the root of a MatrixCommitment over n_rows rows: bool[k] (pmx_matrix_verify_rows - one hash
+    launch over the rows, then the climb of verify_paths).  The root does not bind n_rows, so the verifier states it; an index >= n_rows
+    verifies as False."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    assert rows.ndim == 3 and rows.shape[2] == 4, "rows are [k][row_len][4]"
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    paths = np.ascontiguousarray(paths, dtype=np.uint64)
+    root = np.ascontiguousarray(root, dtype=np.uint64).reshape(4)
+    depth, _ = merkle_ragged_shape(n_rows, arity)
+    assert paths.size == idx.shape[0] * depth * (arity - 1) * 4, "paths are [k][depth][arity - 1][4] for the depth of (n_rows, arity)"
+    return parameters.context(device).matrix_verify_rows(rows, idx, paths, depth, arity, n_rows, root).astype(bool)

@@ -157,6 +157,20 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
+def _matrix_ptr(m):
+    """a numpy array (C-contiguous u64) or a raw host address"""
+    return ctypes.c_void_p(m) if isinstance(m, int) else ctypes.c_void_p(m.ctypes.data)
+
+
+def matrix_rows(matrix: np.ndarray, n_rows: int, row_len: int, layout: int, indices) -> np.ndarray:
+    """rows indices[i] of the flat matrix [n_rows * row_len][4] as [k][row_len][4], row-major whatever the layout (pmx_matrix_rows: host
+    only; an index >= n_rows is a PmxError and nothing is written)"""
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    out = np.zeros((idx.shape[0], row_len, 4), dtype=np.uint64)
+    _lib.check(_lib.lib().pmx_matrix_rows(_matrix_ptr(matrix), n_rows, row_len, layout, _ptr(idx), idx.shape[0], _ptr(out)))
+    return out
+
+
 def c_config(cfg: "PoseidonConfig") -> "_lib.PmxConfig":
     """pmx_config view of a PoseidonConfig (borrows cfg.ark / cfg.mds: keep `cfg` alive while it is used)."""
     c = _lib.PmxConfig()
@@ -428,6 +442,31 @@ class Context:
         """leaf updates of a device-resident node array of the ragged layout, enqueue only; d_work: [k][(arity + 1) * 4] u64 of scratch.
         An index >= n_leaves is ignored."""
         _lib.check(_lib.lib().pmx_merkle_ragged_update_dev(self._h, d_nodes, n_leaves, arity, d_indices, d_new_leaves, k, d_work, stream))
+
+    # ---- matrix commitments: `matrix` is the flat element array [n_rows * row_len][4] in the given layout (a pointer-sized int: a raw
+    # host address, page-locked memory of pmx_host_alloc for instance) ---------
+    def matrix_leaves(self, matrix, n_rows: int, row_len: int, layout: int) -> np.ndarray:
+        """[n_rows][4]: leaf_i = (new; absorb(row i); squeeze_native(1))[0] (pmx_matrix_leaves)"""
+        out = np.zeros((n_rows, 4), dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_matrix_leaves(self._h, _matrix_ptr(matrix), n_rows, row_len, layout, _ptr(out)))
+        return out
+
+    def matrix_commit(self, matrix, n_rows: int, row_len: int, layout: int, arity: int, want_nodes: bool = True, want_root: bool = True):
+        """(nodes, root) of the tree of `arity` over the row digests, the leaves never leaving the device (pmx_matrix_commit); either is
+        None when not asked for"""
+        _, n_nodes = merkle_ragged_shape(n_rows, arity)
+        nodes = np.zeros((n_nodes, 4), dtype=np.uint64) if want_nodes else None
+        root = np.zeros(4, dtype=np.uint64) if want_root else None
+        _lib.check(_lib.lib().pmx_matrix_commit(self._h, _matrix_ptr(matrix), n_rows, row_len, layout, arity, _ptr(nodes), _ptr(root)))
+        return nodes, root
+
+    def matrix_verify_rows(self, rows, indices, paths, depth: int, arity: int, n_rows: int, root) -> np.ndarray:
+        """k opened rows [k][row_len][4] with their paths [k][depth][arity - 1][4] against the root (pmx_matrix_verify_rows): uint8[k]"""
+        k, row_len = rows.shape[0], rows.shape[1]
+        ok = np.zeros(k, dtype=np.uint8)
+        _lib.check(_lib.lib().pmx_matrix_verify_rows(self._h, _ptr(rows), row_len, _ptr(indices), _ptr(paths) if paths.size else None, depth,
+                                                     arity, n_rows, k, _ptr(root), _ptr(ok)))
+        return ok
 
     # ---- device-pointer entry points (only enqueue; pointers are raw device addresses) ---------
     def permute_batch_dev(self, d_states: int, n: int, stream: int = 0) -> None:
