@@ -168,6 +168,17 @@ extern "C" {
                            rows_out: *mut u64) -> c_int;
     pub fn pmx_matrix_verify_rows(ctx: *mut pmx_ctx, rows: *const u64, row_len: usize, indices: *const u64, paths: *const u64, depth: usize,
                                   arity: u32, n_rows: usize, k: usize, root: *const u64, ok_out: *mut u8) -> c_int;
+    // trees of a fixed depth (no counterpart in the reference): empty positions are default leaves, leaves are appended in place and the
+    // caller keeps the frontier [depth][arity - 1] and the leaf count; host buffers only (no device-resident form, no forest, no
+    // device-group form)
+    pub fn pmx_merkle_fixed_defaults(ctx: *mut pmx_ctx, default_leaf: *const u64, arity: u32, depth: usize, defaults_out: *mut u64) -> c_int;
+    pub fn pmx_merkle_frontier_append(ctx: *mut pmx_ctx, arity: u32, depth: usize, defaults: *const u64, frontier_in: *const u64, n_leaves: usize,
+                                      new_leaves: *const u64, m: usize, frontier_out: *mut u64, root: *mut u64) -> c_int;
+    pub fn pmx_merkle_fixed_shape(n_leaves: usize, arity: u32, depth: usize, n_nodes: *mut usize) -> c_int;
+    pub fn pmx_merkle_fixed(ctx: *mut pmx_ctx, leaves: *const u64, n_leaves: usize, arity: u32, depth: usize, defaults: *const u64,
+                            nodes: *mut u64, root: *mut u64) -> c_int;
+    pub fn pmx_merkle_fixed_paths(nodes: *const u64, n_leaves: usize, arity: u32, depth: usize, defaults: *const u64, indices: *const u64,
+                                  k_paths: usize, paths_out: *mut u64) -> c_int;
     // device memory for the *_dev entry points
     pub fn pmx_device_alloc(device: c_int, d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_device_free(device: c_int, d_ptr: *mut c_void) -> c_int;

@@ -308,6 +308,39 @@ impl<F: PrimeField> BatchPoseidon<F> {
                                                    limbs(core::slice::from_ref(root)), ok.as_mut_ptr()) });
         ok.into_iter().map(|b| b != 0).collect()
     }
+    /// Digests of the empty subtrees of a tree of `arity` and fixed `depth` (`pmx_merkle_fixed_defaults`; no counterpart in the
+    /// reference): `e[0] = default_leaf`, `e[l + 1]` the compression of `arity` copies of `e[l]`; `depth + 1` elements, computed once.
+    pub fn merkle_fixed_defaults(&self, default_leaf: &F, arity: u32, depth: usize) -> Vec<F> {
+        let mut defaults = vec![F::zero(); depth + 1];
+        check(unsafe { ffi::pmx_merkle_fixed_defaults(self.ctx.0, limbs(core::slice::from_ref(default_leaf)), arity, depth, limbs_mut(&mut defaults)) });
+        defaults
+    }
+    /// Appends `new_leaves` to the incremental tree that `frontier` (`[depth][arity - 1]`, all zero for the empty tree) and `n_leaves`
+    /// stand for (`pmx_merkle_frontier_append`): the frontier is replaced in place, `n_leaves` grows, and the root of the tree padded
+    /// with the default leaf comes back.  At most `depth` compression launches per piece whatever the number of leaves.
+    pub fn merkle_frontier_append(&self, arity: u32, depth: usize, defaults: &[F], frontier: &mut [F], n_leaves: &mut usize, new_leaves: &[F]) -> F {
+        assert_eq!(defaults.len(), depth + 1, "defaults is not [depth + 1]");
+        assert_eq!(frontier.len(), depth * (arity as usize - 1), "frontier is not [depth][arity - 1]");
+        assert!(!new_leaves.is_empty(), "nothing to append");
+        let mut root = F::zero();
+        let io = limbs_mut(frontier);
+        check(unsafe { ffi::pmx_merkle_frontier_append(self.ctx.0, arity, depth, limbs(defaults), io as *const u64, *n_leaves, limbs(new_leaves),
+                                                       new_leaves.len(), io, limbs_mut(core::slice::from_mut(&mut root))) });
+        *n_leaves += new_leaves.len();
+        root
+    }
+    /// The dense tree of `arity` and fixed `depth` over `leaves` (at least one), every other position a default leaf
+    /// (`pmx_merkle_fixed`): the complete and the partial nodes of every level, leaves first and root last (`pmx_merkle_fixed_shape`).
+    /// Openings are `pmx_merkle_fixed_paths` on them and verify through `merkle_ary_verify_paths`.
+    pub fn merkle_fixed(&self, leaves: &[F], arity: u32, depth: usize, defaults: &[F]) -> Vec<F> {
+        assert_eq!(defaults.len(), depth + 1, "defaults is not [depth + 1]");
+        let mut n_nodes = 0usize;
+        check(unsafe { ffi::pmx_merkle_fixed_shape(leaves.len(), arity, depth, &mut n_nodes) });
+        let mut nodes = vec![F::zero(); n_nodes];
+        check(unsafe { ffi::pmx_merkle_fixed(self.ctx.0, limbs(leaves), leaves.len(), arity, depth, limbs(defaults), limbs_mut(&mut nodes),
+                                             core::ptr::null_mut()) });
+        nodes
+    }
     /// 2-to-1 tree over `leaves` (power of two): all nodes, leaves first, root last.
     pub fn merkle(&self, leaves: &[F]) -> Vec<F> {
         let mut nodes = vec![F::zero(); 2 * leaves.len() - 1];

@@ -482,6 +482,49 @@ int pmx_merkle_ragged_verify_paths_dev(pmx_ctx *ctx, const uint64_t *d_leaves, c
 int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity, const uint64_t *d_indices,
                                  const uint64_t *d_new_leaves, size_t k, uint64_t *d_work, void *stream);
 
+/* ---- Merkle trees of a fixed depth: empty positions are default leaves, leaves are appended in place ---
+ * Note-commitment trees, identity groups and rollup state trees are INCREMENTAL trees: arity k (2 <= k <= rate), a fixed depth D
+ * (1 <= D <= 64, k^D <= 2^64), leaves appended left to right, every position not yet filled counting as a default leaf e[0] and an empty
+ * subtree of height l as e[l] = (new; absorb(k copies of e[l-1]); squeeze_native(1))[0].  The tree over n leaves, 0 <= n <= k^D, is BY
+ * DEFINITION pmx_merkle_ary over the leaf row padded with e[0] to k^D leaves - which at depth 32 nobody can hold.  (No counterpart in the
+ * reference, which has no tree.)
+ * Node j of level l is complete iff (j + 1) k^l <= n and partial iff it is not complete and j k^l < n; a level has at most one partial
+ *   node.  The frontier is, per level l < D, the complete nodes k floor(f_l / k) .. f_l - 1 with f_l = floor(n / k^l): digit l of n in base
+ *   k of them.  frontier: [D][k - 1][4]; slots at or beyond the digit are zero words on output and ignored on input, so equal trees have
+ *   equal frontier bytes.  (frontier, n) is all a caller keeps: D (k - 1) digests and a count.
+ * pmx_merkle_fixed_defaults: defaults_out [D + 1][4] = e[0 .. D] from the caller's default leaf; D dependent launches of one unit, done once.
+ * pmx_merkle_frontier_append: m new leaves behind the n_leaves the frontier stands for.  Per level ONE full-row compression launch, on
+ *   the engine pmx_ctx_engine_info(ctx, PMX_OP_COMPRESS, parents, arity) names (arity 2: the 2-to-1 launch, the quad engine included),
+ *   over a row that holds the level's frontier nodes, its newly complete nodes (level 0: the new leaves), its partial node and copies of
+ *   e[l] up to a multiple of k; the pads and the frontier nodes of all levels are laid out by one launch before the walk, the new
+ *   frontier and the root come back in one download: at most D compression launches per piece, nothing per leaf, no short row.  A long
+ *   append runs in pieces of a bounded number of leaves; appends compose exactly, so pieces change no byte.  frontier_in may be NULL
+ *   iff n_leaves = 0; frontier_out may alias frontier_in; root (may be NULL) receives node 0 of level D, which is a complete node only
+ *   when n_leaves + m = k^D.  m = 0 is legal and returns the current root - except over a FULL tree, whose frontier holds no node: with
+ *   n_leaves = k^D and m = 0 a non-NULL root is PMX_ERR_ARG.
+ * pmx_merkle_fixed_shape (host only): the dense form stores max(1, ceil(n_leaves / k^l)) nodes of level l = 0 .. D - the complete nodes
+ *   and the partial one -, packed, leaves first and root last; n_leaves >= 1.
+ * pmx_merkle_fixed: the dense form: the same walk from the empty frontier, every computed node kept (nodes [n_nodes][4] and root may be
+ *   NULL).  At n_leaves = k^D the array is byte for byte that of pmx_merkle_ary.  `nodes` is written piece by piece.
+ * pmx_merkle_fixed_paths (host only): paths_out [k_paths][D][k - 1][4] in the layout of pmx_merkle_ary_paths; a sibling beyond its
+ *   level's stored width is e[l].  Every index is checked (< n_leaves) before anything is written.  The paths are accepted unchanged by
+ *   pmx_merkle_ary_verify_paths(..., depth, arity, ...): there is no verifier of its own.
+ * Like every host-buffer entry these serialise on the context's lock and run inside the catch-all; device scratch is the context's staging.
+ * What the family lacks: host buffers only (no *_dev entry and no graph-capturable form), no leaf update of a fixed-depth tree
+ *   (pmx_merkle_ary_update on a dense array remains the route), no forest and no device-group form.
+ * Errors, nothing launched or written on any: PMX_ERR_ARG for null pointers, arity < 2, depth = 0, depth > 64, k^D beyond 64 bits (k^D =
+ *   2^64 is accepted), n_leaves + m > k^D, n_leaves = 0 of a dense tree, byte sizes that overflow size_t; PMX_ERR_CONFIG for arity > rate. */
+int pmx_merkle_fixed_defaults(pmx_ctx *ctx, const uint64_t default_leaf[PMX_LIMBS], uint32_t arity, size_t depth,
+                              uint64_t *defaults_out /* [depth + 1][4] */);
+int pmx_merkle_frontier_append(pmx_ctx *ctx, uint32_t arity, size_t depth, const uint64_t *defaults,
+                               const uint64_t *frontier_in /* may be NULL iff n_leaves == 0 */, size_t n_leaves, const uint64_t *new_leaves,
+                               size_t m, uint64_t *frontier_out, uint64_t *root /* may be NULL */);
+int pmx_merkle_fixed_shape(size_t n_leaves, uint32_t arity, size_t depth, size_t *n_nodes);
+int pmx_merkle_fixed(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *defaults,
+                     uint64_t *nodes /* may be NULL */, uint64_t *root /* may be NULL */);
+int pmx_merkle_fixed_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *defaults,
+                           const uint64_t *indices, size_t k_paths, uint64_t *paths_out /* [k_paths][depth][arity - 1][4] */);
+
 /* ---- matrix commitments: the rows of a trace / LDE matrix as the leaves of a tree ---------------------
  * A prover holds a matrix of n_rows rows and row_len columns, almost always column-major (one column per polynomial), and commits to
  * its ROWS: leaf_i = (new; absorb(row i); squeeze_native(1))[0], the reference sponge's own answer for a row of any length - absorb

@@ -43,6 +43,11 @@ int pmx_test_grind_chunk(uint64_t candidates);
  * host loop. */
 int pmx_test_matrix_slab_rows(uint64_t rows);
 
+/* pmx_merkle_frontier_append and pmx_merkle_fixed walk their leaves in pieces of `leaves` leaves instead of the product's measured piece
+ * (0: the product's again), so that an append of a thousand leaves takes the multi-piece path - the frontier handed from piece to piece on
+ * the host - and the piece sweep of tools/merkle_fixed_rate.py runs every size through the product's own host loop. */
+int pmx_test_merkle_fixed_piece(uint64_t leaves);
+
 /* The strided hash kernel of the matrix entries on the caller's own device buffers: d_leaves [n_rows][4] receives
  * (new; absorb(row i); squeeze_native(1))[0] of the rows whose element k is at d_matrix + (i * row_stride + k * elem_stride) * 4 -
  * (row_len, 1) for a row-major matrix, (1, ld) for a column-major one of leading dimension ld.  It only enqueues on `stream`; both

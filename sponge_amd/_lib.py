@@ -167,6 +167,12 @@ SIGNATURES = {
     "pmx_merkle_ragged_verify_paths_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _u64p, _u64p, _sz, ctypes.c_uint32, _sz, _sz, _u64p,
                                                           ctypes.c_void_p, _u64p, ctypes.c_void_p]),
     "pmx_merkle_ragged_update_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _u64p, _u64p, _sz, _u64p, ctypes.c_void_p]),
+    # trees of a fixed depth (host buffers only)
+    "pmx_merkle_fixed_defaults": (ctypes.c_int, [ctypes.c_void_p, _u64p, ctypes.c_uint32, _sz, _u64p]),
+    "pmx_merkle_frontier_append": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, _sz, _u64p, _u64p, _sz, _u64p, _sz, _u64p, _u64p]),
+    "pmx_merkle_fixed_shape": (ctypes.c_int, [_sz, ctypes.c_uint32, _sz, ctypes.POINTER(_sz)]),
+    "pmx_merkle_fixed": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _sz, _u64p, _u64p, _u64p]),
+    "pmx_merkle_fixed_paths": (ctypes.c_int, [_u64p, _sz, ctypes.c_uint32, _sz, _u64p, _u64p, _sz, _u64p]),
     # matrix commitments (layout, arity: uint32_t)
     "pmx_matrix_leaves": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, ctypes.c_uint32, _u64p]),
     "pmx_matrix_commit": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p]),
@@ -210,6 +216,7 @@ TEST_HOOK_SIGNATURES = {
     "pmx_mgpu_test_shared_device": (ctypes.c_int, [ctypes.c_int]),
     "pmx_test_grind_chunk": (ctypes.c_int, [ctypes.c_uint64]),
     "pmx_test_matrix_slab_rows": (ctypes.c_int, [ctypes.c_uint64]),
+    "pmx_test_merkle_fixed_piece": (ctypes.c_int, [ctypes.c_uint64]),
     "pmx_test_matrix_leaves_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _sz, _sz, _u64p, ctypes.c_void_p]),
 }
 

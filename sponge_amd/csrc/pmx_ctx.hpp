@@ -80,6 +80,10 @@ uint64_t grind_chunk();
 // PMX_MATRIX_SLAB_BYTES of device memory holds (pmx_matrix_shape.hpp: matrix_slab_rows) - or what pmx_test_matrix_slab_rows set, so that
 // a matrix of a few hundred rows takes the multi-slab path and the slab sweep runs every size through the product's own host loop.
 uint64_t matrix_slab_rows_hook();
+// Leaves per piece of pmx_merkle_frontier_append and pmx_merkle_fixed (pmx_merkle.cpp), the same way: the constant of pmx_hooks.cpp in
+// the shipped library, or what pmx_test_merkle_fixed_piece set, so that an append of a thousand leaves takes the multi-piece path and the
+// piece sweep of tools/merkle_fixed_rate.py runs every size through the product's own host loop.
+uint64_t merkle_fixed_piece();
 
 #define PMX_BIND(ctx)                                                                \
     ::pmx::DeviceGuard device_guard_((ctx)->device);                                 \

@@ -1661,6 +1661,22 @@ hipError_t launch_node_children(const uint64_t *nodes, const uint64_t *indices, 
     return hipGetLastError();
 }
 
+// ---- fixed-depth trees (pmx_merkle_fixed*, pmx_merkle_frontier_append) ----------------------------------------------------------------
+// Pure data movement around the compression launches, driven by a list the host built (pmx_merkle_frontier.hpp): entry i is the pair
+// (list[2 i], list[2 i + 1]) = (destination element, source element) of `elems`, two lanes per entry, one 16-byte half each.  It lays the
+// uploaded frontier nodes and the default digests into the levels' rows before the walk and collects the new frontier and the root behind
+// it.  Sources and destinations of one launch never overlap (the host's lists read what was uploaded or computed and write elsewhere),
+// but they lie in one array: no __restrict__ on it.
+__global__ void __launch_bounds__(256) node_place_kernel(uint4 *elems, const uint64_t *__restrict__ list, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, i = gid >> 1;
+    if (i >= k) return;
+    elems[list[2 * i] * 2 + (gid & 1)] = elems[list[2 * i + 1] * 2 + (gid & 1)];
+}
+hipError_t launch_node_place(uint64_t *elems, const uint64_t *list, size_t k, hipStream_t st) {
+    hipLaunchKernelGGL(node_place_kernel, dim3((unsigned)((k * 2 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<uint4 *>(elems), list, k);
+    return hipGetLastError();
+}
+
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,
                              uint64_t *pairs, size_t k, hipStream_t st) {
     hipLaunchKernelGGL(path_pairs_kernel, dim3((unsigned)((k * 4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),

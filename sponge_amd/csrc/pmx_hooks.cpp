@@ -11,6 +11,8 @@
 namespace pmx {
 // Candidates per launch of pmx_sponge_grind (pmx_api.cpp), chosen from the sweep of profiles/grind/README.md.
 static constexpr uint64_t kGrindChunk = (uint64_t)1 << 21;
+// Leaves per piece of pmx_merkle_frontier_append / pmx_merkle_fixed (pmx_merkle.cpp); how it was chosen: profiles/merkle_fixed/README.md.
+static constexpr uint64_t kMerkleFixedPiece = (uint64_t)1 << 22;
 }  // namespace pmx
 
 #ifdef PMX_TEST_HOOKS
@@ -29,6 +31,15 @@ extern "C" int pmx_test_matrix_slab_rows(uint64_t rows) {
     return PMX_OK;
 }
 uint64_t pmx::matrix_slab_rows_hook() { return g_matrix_slab_rows.load(); }
+static std::atomic<uint64_t> g_merkle_fixed_piece{0};   // 0: the product's
+extern "C" int pmx_test_merkle_fixed_piece(uint64_t leaves) {
+    g_merkle_fixed_piece.store(leaves);
+    return PMX_OK;
+}
+uint64_t pmx::merkle_fixed_piece() {
+    const uint64_t set = g_merkle_fixed_piece.load();
+    return set ? set : kMerkleFixedPiece;
+}
 // the strided hash kernel of the matrix entries on the caller's own device buffers and stream, out_len = 1: enqueue only
 extern "C" int pmx_test_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
                                           uint64_t *d_leaves, void *stream) {
@@ -42,4 +53,5 @@ extern "C" int pmx_test_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix
 #else
 uint64_t pmx::grind_chunk() { return kGrindChunk; }
 uint64_t pmx::matrix_slab_rows_hook() { return 0; }
+uint64_t pmx::merkle_fixed_piece() { return kMerkleFixedPiece; }
 #endif

@@ -116,5 +116,8 @@ hipError_t launch_paths_gather_ragged(const uint64_t *nodes, size_t n_leaves, ui
                                       uint64_t *paths, size_t k, hipStream_t st);
 hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first,
                                         uint64_t width, uint32_t arity, uint64_t *rows, size_t k, hipStream_t st);
+// Fixed-depth trees (pmx_merkle_fixed*, pmx_merkle_frontier_append): elems[list[2 i]] = elems[list[2 i + 1]] for i < k, elements of 4 words
+// of one device array, the pairs built by the host (pmx_merkle_frontier.hpp); no destination is a source of the same launch.  k >= 1.
+hipError_t launch_node_place(uint64_t *elems, const uint64_t *list, size_t k, hipStream_t st);
 
 }  // namespace pmx

@@ -6,7 +6,9 @@
 // launch of a ragged builder is the one pmx_merkle_ary* makes (launch_compress_level on a level that divides is launch_compress_ary,
 // which at arity 2 is launch_compress).  What stays per entry is its name in the null-pointer message, its shape check with its own
 // texts, and the order of its checks; the family picks between the twin gather kernels (a ragged entry launches the bounded one whatever
-// the leaf count).  The *_dev entries only enqueue on the caller's stream: no allocation, no synchronisation.
+// the leaf count).  The *_dev entries only enqueue on the caller's stream: no allocation, no synchronisation.  The trees of a fixed depth
+// (pmx_merkle_fixed*, pmx_merkle_frontier_append, at the end of the file) are the same full-row launches over rows that
+// pmx_merkle_frontier.hpp lays out: host buffers only.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,6 +20,7 @@
 #include "pmx_ctx.hpp"
 #include "pmx_internal.hpp"
 #include "pmx_launch.hpp"
+#include "pmx_merkle_frontier.hpp"
 #include "pmx_merkle_plan.hpp"
 #include "pmx_merkle_shape.hpp"
 
@@ -492,4 +495,192 @@ extern "C" int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, siz
     MerkleShape s;
     if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
     return update_dev(ctx, d_nodes, n_leaves, arity, true, d_indices, d_new_leaves, k, d_work, stream);
+}
+
+// ---- trees of a fixed depth: empty positions are default leaves, leaves are appended in place -----------------------------------------
+namespace {
+
+int frontier_error(FrontierError e) {
+    switch (e) {
+    case FrontierError::ok: return PMX_OK;
+    case FrontierError::arity: return set_error(PMX_ERR_ARG, "arity must be at least 2");
+    case FrontierError::depth: return set_error(PMX_ERR_ARG, "depth must be 1 .. 64");
+    case FrontierError::pow_overflow: return set_error(PMX_ERR_ARG, "arity^depth overflows 64 bits");
+    case FrontierError::too_many: return set_error(PMX_ERR_ARG, "more leaves than the arity^depth positions of the tree");
+    case FrontierError::no_leaves: return set_error(PMX_ERR_ARG, "a tree needs at least one leaf");
+    default: return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
+    }
+}
+
+// One piece of the walk (pmx_merkle_frontier.hpp; the caller holds host_lock and has bound the device): one upload of frontier and default
+// digests, one of the two lists, one of the leaves; the kept nodes and the pads of ALL levels in one launch; one full-row compression
+// launch per level that has rows, on the engine pmx_ctx_engine_info names for its parents; the new frontier and the root gathered in one
+// launch and brought back in one download.  `frontier` ([D][k - 1][4], host) is read in its kept slots and replaced, unused slots zero;
+// `root` [4] receives the root when the plan knows it.  nodes / first: the dense form keeps what the piece computed - the fresh and the
+// partial node of every level above the leaves go to their places in the caller's array, one download per level.
+int fixed_piece(pmx_ctx *ctx, const FrontierPlan &P, const uint64_t *defaults, uint64_t *frontier, const uint64_t *leaves, uint64_t *root,
+                uint64_t *nodes, const size_t *first) {
+    int rc = PMX_OK;
+    const size_t D = P.depth, fe = P.frontier_elements(), n_place = P.place.size() / 2, n_gather = P.gather.size() / 2;
+    std::vector<uint64_t> in((fe + D + 1) * 4), out((fe + 1) * 4), lists(P.place);
+    std::memcpy(in.data(), frontier, fe * 32);
+    std::memcpy(in.data() + fe * 4, defaults, (D + 1) * 32);
+    lists.insert(lists.end(), P.gather.begin(), P.gather.end());
+    void *d0 = nullptr, *d1 = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, P.elements * 32, &d0))) return rc;
+    if ((rc = ctx_scratch(ctx, 1, (lists.size() + 2) * 8, &d1))) return rc;
+    uint64_t *d = (uint64_t *)d0, *d_lists = (uint64_t *)d1;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d + P.in_frontier * 4, in.data(), in.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!lists.empty()) PMX_HIP(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (P.m) PMX_HIP(hipMemcpyAsync(d + (P.level[0].offset + P.level[0].kept) * 4, leaves, (size_t)P.m * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (n_place) PMX_HIP(launch_node_place(d, d_lists, n_place, ctx->stream));
+    for (size_t l = 0; l < D; ++l) {
+        const FrontierLevel &L = P.level[l], &U = P.level[l + 1];
+        if (L.parents)
+            PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d + L.offset * 4, d + (U.offset + U.kept) * 4, P.arity, (size_t)L.parents, ctx->stream));
+    }
+    if (n_gather) PMX_HIP(launch_node_place(d, d_lists + n_place * 2, n_gather, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(out.data(), d + P.out_frontier * 4, out.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (nodes)
+        for (size_t l = 1; l <= D; ++l) {
+            const FrontierLevel &L = P.level[l];
+            if (const size_t count = (size_t)(L.fresh + L.partial))
+                PMX_HIP(hipMemcpyAsync(nodes + (first[l] + (size_t)(L.first + L.kept)) * 4, d + (L.offset + L.kept) * 4, count * 32,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        }
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    if (nodes && P.m) std::memcpy(nodes + (size_t)P.n * 4, leaves, (size_t)P.m * 32);
+    std::memset(frontier, 0, fe * 32);
+    for (size_t l = 0; l < D; ++l)
+        std::memcpy(frontier + l * (P.arity - 1) * 4, out.data() + l * (P.arity - 1) * 4, (size_t)P.level[l].digit * 32);
+    if (P.root_computed) std::memcpy(root, out.data() + fe * 4, 32);
+    else if (P.root_is_default) std::memcpy(root, defaults + D * 4, 32);
+    return PMX_OK;
+}
+
+// m leaves behind the n the frontier stands for, in pieces of merkle_fixed_piece() leaves (appends compose exactly: pieces change no byte);
+// m = 0 is one piece that recomputes the partial nodes and the root.  frontier / root: host temporaries, as for fixed_piece.
+int fixed_walk(pmx_ctx *ctx, uint32_t arity, size_t depth, const uint64_t *defaults, uint64_t n, const uint64_t *leaves, uint64_t m,
+               uint64_t *frontier, uint64_t *root, uint64_t *nodes, const size_t *first) {
+    PMX_BIND(ctx);
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    const uint64_t piece = merkle_fixed_piece();
+    uint64_t done = 0;
+    do {
+        const uint64_t take = m - done < piece ? m - done : piece;
+        FrontierPlan plan;
+        if (int rc = frontier_error(frontier_plan(n + done, take, arity, depth, &plan))) return rc;
+        if (int rc = fixed_piece(ctx, plan, defaults, frontier, leaves + (size_t)done * 4, root, nodes, first)) return rc;
+        done += take;
+    } while (done < m);
+    return PMX_OK;
+}
+
+}  // namespace
+
+extern "C" int pmx_merkle_fixed_defaults(pmx_ctx *ctx, const uint64_t default_leaf[PMX_LIMBS], uint32_t arity, size_t depth, uint64_t *defaults_out) {
+    PMX_ABI_BEGIN("pmx_merkle_fixed_defaults")
+    if (!ctx || !default_leaf || !defaults_out) return set_error(PMX_ERR_ARG, "pmx_merkle_fixed_defaults: null pointer");
+    u128 capacity = 0;
+    if (int rc = frontier_error(frontier_capacity(arity, depth, &capacity))) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    PMX_BIND(ctx);
+    int rc = PMX_OK;
+    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    // slot 0: e [depth + 1][4] | rows [depth][arity][4];  slot 1: the list that copies e[l] into the arity slots of row l
+    std::vector<uint64_t> list, e((depth + 1) * 4);
+    for (size_t l = 0; l < depth; ++l)
+        for (uint32_t j = 0; j < arity; ++j) list.push_back(depth + 1 + l * arity + j), list.push_back(l);
+    void *d0 = nullptr, *d1 = nullptr;
+    if ((rc = ctx_scratch(ctx, 0, (depth + 1 + depth * arity) * 32, &d0))) return rc;
+    if ((rc = ctx_scratch(ctx, 1, list.size() * 8, &d1))) return rc;
+    uint64_t *d = (uint64_t *)d0, *d_list = (uint64_t *)d1;
+    StreamDrain drain{ctx};
+    PMX_HIP(hipMemcpyAsync(d, default_leaf, 32, hipMemcpyHostToDevice, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(d_list, list.data(), list.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t l = 0; l < depth; ++l) {      // e[l + 1] depends on e[l]: `depth` launches of one unit each
+        PMX_HIP(launch_node_place(d, d_list + l * arity * 2, arity, ctx->stream));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d + (depth + 1 + l * arity) * 4, d + (l + 1) * 4, arity, 1, ctx->stream));
+    }
+    PMX_HIP(hipMemcpyAsync(e.data(), d, e.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(defaults_out, e.data(), e.size() * 8);
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_frontier_append(pmx_ctx *ctx, uint32_t arity, size_t depth, const uint64_t *defaults, const uint64_t *frontier_in,
+                                          size_t n_leaves, const uint64_t *new_leaves, size_t m, uint64_t *frontier_out, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_frontier_append")
+    if (!ctx || !defaults || !frontier_out || (!frontier_in && n_leaves) || (!new_leaves && m))
+        return set_error(PMX_ERR_ARG, "pmx_merkle_frontier_append: null pointer");
+    u128 capacity = 0;
+    if (int rc = frontier_error(frontier_capacity(arity, depth, &capacity))) return rc;
+    if ((u128)n_leaves + m > capacity || (u128)n_leaves + m > UINT64_MAX) return frontier_error(FrontierError::too_many);
+    if (m > (SIZE_MAX / 32) / 4) return frontier_error(FrontierError::bytes_overflow);
+    if (root && m == 0 && (u128)n_leaves == capacity)
+        return set_error(PMX_ERR_ARG, "the frontier of a full tree holds no node: its root cannot be recomputed (root must be NULL)");
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    std::vector<uint64_t> frontier(depth * (size_t)(arity - 1) * 4, 0);
+    uint64_t top[4] = {0, 0, 0, 0};
+    if (frontier_in) std::memcpy(frontier.data(), frontier_in, frontier.size() * 8);
+    if (int rc = fixed_walk(ctx, arity, depth, defaults, n_leaves, new_leaves, m, frontier.data(), top, nullptr, nullptr)) return rc;
+    std::memcpy(frontier_out, frontier.data(), frontier.size() * 8);
+    if (root) std::memcpy(root, top, 32);
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+extern "C" int pmx_merkle_fixed_shape(size_t n_leaves, uint32_t arity, size_t depth, size_t *n_nodes) {
+    PMX_ABI_BEGIN("pmx_merkle_fixed_shape")
+    if (!n_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_fixed_shape: null pointer");
+    std::vector<size_t> first;
+    if (int rc = frontier_error(fixed_shape(n_leaves, arity, depth, &first))) return rc;
+    *n_nodes = first[depth + 1];
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// The dense form: the walk from the empty frontier, every computed node kept.  `nodes` is written piece by piece.
+extern "C" int pmx_merkle_fixed(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *defaults,
+                                uint64_t *nodes, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_fixed")
+    if (!ctx || !leaves || !defaults) return set_error(PMX_ERR_ARG, "pmx_merkle_fixed: null pointer");
+    std::vector<size_t> first;
+    if (int rc = frontier_error(fixed_shape(n_leaves, arity, depth, &first))) return rc;
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    std::vector<uint64_t> frontier(depth * (size_t)(arity - 1) * 4, 0);
+    uint64_t top[4] = {0, 0, 0, 0};
+    if (int rc = fixed_walk(ctx, arity, depth, defaults, 0, leaves, n_leaves, frontier.data(), top, nodes, first.data())) return rc;
+    if (root) std::memcpy(root, top, 32);
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// Openings of the dense form, on the host: the layout of pmx_merkle_ary_paths; a sibling at or beyond its level's stored width is an
+// empty subtree, e[level].  Every index is checked before anything is written.
+extern "C" int pmx_merkle_fixed_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *defaults,
+                                      const uint64_t *indices, size_t k_paths, uint64_t *paths_out) {
+    PMX_ABI_BEGIN("pmx_merkle_fixed_paths")
+    if (!nodes || !defaults || ((!indices || !paths_out) && k_paths)) return set_error(PMX_ERR_ARG, "pmx_merkle_fixed_paths: null pointer");
+    std::vector<size_t> first;
+    if (int rc = frontier_error(fixed_shape(n_leaves, arity, depth, &first))) return rc;
+    if (k_paths > (SIZE_MAX / 32) / (depth * (size_t)(arity - 1))) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    for (size_t i = 0; i < k_paths; ++i)
+        if (indices[i] >= n_leaves) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[i]);
+    const size_t sib = arity - 1;
+    for (size_t i = 0; i < k_paths; ++i) {
+        size_t idx = (size_t)indices[i];
+        for (size_t level = 0; level < depth; ++level, idx /= arity) {
+            const size_t digit = idx % arity, base = idx - digit, width = first[level + 1] - first[level];
+            uint64_t *row = paths_out + (i * depth + level) * sib * 4;
+            for (size_t s = 0; s < sib; ++s) {
+                const size_t child = base + (s < digit ? s : s + 1);
+                std::memcpy(row + s * 4, child < width ? nodes + (first[level] + child) * 4 : defaults + level * 4, 32);
+            }
+        }
+    }
+    return PMX_OK;
+    PMX_ABI_END
 }

@@ -475,4 +475,49 @@ inline std::vector<bool> matrix_verify_rows(const PoseidonConfig &parameters, co
     return std::vector<bool>(ok.begin(), ok.end());
 }
 
+// Trees of a fixed depth (pmx_merkle_fixed*, pmx_merkle_frontier_append; no counterpart in the reference): arity^depth leaf positions,
+// every position not yet filled a default leaf.  An append-only tree keeps its frontier - depth * (arity - 1) digests - and its leaf
+// count; append() costs at most `depth` compression launches per piece whatever the number of leaves.  Host buffers only.
+class IncrementalMerkleTree {
+public:
+    IncrementalMerkleTree(const PoseidonConfig &parameters, size_t depth, uint32_t arity = 2, const Fp &default_leaf = Fp{}, int device = 0)
+        : ctx_(parameters.context(device)), arity_(arity), depth_(depth), defaults_(depth + 1), frontier_(depth * (arity - 1)) {
+        static_assert(sizeof(Fp) == 32, "a field element is four limbs");
+        check(pmx_merkle_fixed_defaults(ctx_->get(), default_leaf.l.data(), arity, depth, defaults_[0].l.data()));
+        root_ = defaults_[depth];
+    }
+    // the new root
+    const Fp &append(const std::vector<Fp> &leaves) {
+        if (leaves.empty()) return root_;
+        uint64_t *io = frontier_.empty() ? nullptr : frontier_[0].l.data();
+        check(pmx_merkle_frontier_append(ctx_->get(), arity_, depth_, defaults_[0].l.data(), io, n_leaves_, leaves[0].l.data(), leaves.size(), io,
+                                         root_.l.data()));
+        n_leaves_ += leaves.size();
+        return root_;
+    }
+    const Fp &root() const { return root_; }
+    size_t n_leaves() const { return n_leaves_; }
+    const std::vector<Fp> &frontier() const { return frontier_; }     // [depth][arity - 1], unused slots zero
+    const std::vector<Fp> &defaults() const { return defaults_; }     // [depth + 1]
+
+private:
+    std::shared_ptr<Context> ctx_;
+    uint32_t arity_;
+    size_t depth_, n_leaves_ = 0;
+    std::vector<Fp> defaults_, frontier_;
+    Fp root_{};
+};
+// The dense form: the complete and the partial nodes of every level, leaves first and root last (pmx_merkle_fixed_shape); openings are
+// pmx_merkle_fixed_paths on them and verify through pmx_merkle_ary_verify_paths.
+inline std::vector<Fp> merkle_fixed(const PoseidonConfig &parameters, const std::vector<Fp> &leaves, size_t depth, const std::vector<Fp> &defaults,
+                                    uint32_t arity = 2, int device = 0) {
+    size_t n_nodes = 0;
+    check(pmx_merkle_fixed_shape(leaves.size(), arity, depth, &n_nodes));
+    if (defaults.size() != depth + 1) throw std::invalid_argument("defaults are [depth + 1]");
+    std::vector<Fp> nodes(n_nodes);
+    check(pmx_merkle_fixed(parameters.context(device)->get(), leaves[0].l.data(), leaves.size(), arity, depth, defaults[0].l.data(), nodes[0].l.data(),
+                           nullptr));
+    return nodes;
+}
+
 }  // namespace pmx_host

@@ -14,7 +14,7 @@ import numpy as np
 import ctypes
 
 from . import _lib
-from .poseidon import PoseidonConfig, matrix_rows, merkle_ragged_shape
+from .poseidon import PoseidonConfig, matrix_rows, merkle_fixed_paths, merkle_ragged_shape
 
 
 class MerkleTree:
@@ -147,6 +147,65 @@ class MerkleTree:
         gather = ctx.merkle_ragged_paths_dev if self.ragged else ctx.merkle_ary_paths_dev
         self._with_device_blocks([nodes, idx, out.nbytes], lambda d: gather(d[0], self.n_leaves, self.arity, d[1], idx.shape[0], d[2], None), {2: out})
         return out
+
+
+def _default_leaf(parameters: PoseidonConfig, default_leaf) -> np.ndarray:
+    """an integer is a field element (converted to the library's form), anything else is the element's four words"""
+    if isinstance(default_leaf, (int, np.integer)):
+        return np.ascontiguousarray(parameters.field.from_ints([int(default_leaf)]), dtype=np.uint64).reshape(4)
+    return np.ascontiguousarray(default_leaf, dtype=np.uint64).reshape(4)
+
+
+class FixedMerkleTree:
+    """The dense tree of a fixed depth over n >= 1 leaves, every other of the arity^depth positions a default leaf (pmx_merkle_fixed;
+    MerkleTree.fixed makes it): `.nodes` holds the complete and the partial nodes of every level, leaves first and root last,
+    `.defaults` [depth + 1][4] the digests of the empty subtrees, `.open(indices)` the openings [k][depth][arity - 1][4], which
+    verify_paths(..., arity=arity) of a tree of arity^depth leaves accepts (at arity 2: reshape to [k][depth][4])."""
+
+    def __init__(self, parameters: PoseidonConfig, leaves, depth: int, arity: int = 2, default_leaf=0, device: int = 0):
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        ctx = parameters.context(device)
+        self.parameters, self.device, self.arity, self.depth, self.n_leaves = parameters, device, arity, depth, leaves.shape[0]
+        self.defaults = ctx.merkle_fixed_defaults(_default_leaf(parameters, default_leaf), arity, depth)
+        self.nodes, self._root = ctx.merkle_fixed(leaves, arity, depth, self.defaults)
+
+    @property
+    def root(self) -> np.ndarray:
+        return self._root
+
+    def open(self, indices) -> np.ndarray:
+        return merkle_fixed_paths(self.nodes, self.n_leaves, self.arity, self.depth, self.defaults, indices)
+
+
+MerkleTree.fixed = staticmethod(lambda parameters, leaves, depth, arity=2, default_leaf=0, device=0:
+                                FixedMerkleTree(parameters, leaves, depth, arity, default_leaf, device))
+
+
+class IncrementalMerkleTree:
+    """An append-only tree of a fixed depth (a note-commitment tree, an identity group, a rollup's state tree): what is kept is the
+    frontier - depth * (arity - 1) digests - and the leaf count; `.append(leaves)` is pmx_merkle_frontier_append, at most `depth`
+    compression launches per piece whatever the number of leaves.  `.root` is the root of the tree padded with the default leaf."""
+
+    def __init__(self, parameters: PoseidonConfig, depth: int, arity: int = 2, default_leaf=0, device: int = 0):
+        self.parameters, self.device, self.arity, self.depth = parameters, device, arity, depth
+        self.defaults = parameters.context(device).merkle_fixed_defaults(_default_leaf(parameters, default_leaf), arity, depth)
+        self.frontier = np.zeros((depth, arity - 1, 4), dtype=np.uint64)
+        self.n_leaves = 0
+        self._root = self.defaults[depth].copy()
+
+    @property
+    def root(self) -> np.ndarray:
+        return self._root
+
+    def append(self, leaves) -> np.ndarray:
+        """append leaves [m][4]; returns the new root"""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        if leaves.shape[0] == 0:
+            return self._root
+        self.frontier, self._root = self.parameters.context(self.device).merkle_frontier_append(
+            self.arity, self.depth, self.defaults, self.frontier, self.n_leaves, leaves)
+        self.n_leaves += leaves.shape[0]
+        return self._root
 
 
 def verify_paths(parameters: PoseidonConfig, leaves: np.ndarray, indices, paths: np.ndarray, root: np.ndarray,

@@ -199,6 +199,25 @@ def merkle_ragged_shape(n_leaves: int, arity: int) -> Tuple[int, int]:
     return depth.value, n_nodes.value
 
 
+def merkle_fixed_shape(n_leaves: int, arity: int, depth: int) -> int:
+    """n_nodes of the dense tree of `arity` and fixed `depth` over n_leaves >= 1 leaves: level l stores max(1, ceil(n_leaves / arity^l))
+    nodes (pmx_merkle_fixed_shape; host only)."""
+    n_nodes = ctypes.c_size_t(0)
+    _lib.check(_lib.lib().pmx_merkle_fixed_shape(n_leaves, arity, depth, ctypes.byref(n_nodes)))
+    return n_nodes.value
+
+
+def merkle_fixed_paths(nodes, n_leaves: int, arity: int, depth: int, defaults, indices) -> np.ndarray:
+    """[k][depth][arity - 1][4]: the openings of the dense tree (pmx_merkle_fixed_paths; host only); a sibling beyond its level's stored
+    width is the default digest of the level.  An index >= n_leaves is a PmxError."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
+    defaults = np.ascontiguousarray(defaults, dtype=np.uint64)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    out = np.zeros((idx.shape[0], depth, arity - 1, 4), dtype=np.uint64)
+    _lib.check(_lib.lib().pmx_merkle_fixed_paths(_ptr(nodes), n_leaves, arity, depth, _ptr(defaults), _ptr(idx), idx.shape[0], _ptr(out)))
+    return out
+
+
 def varlen_rows(elems, offsets=None) -> Tuple[np.ndarray, np.ndarray]:
     """(elems [*][4], offsets [n+1]) of variable-length rows, contiguous u64: a list of [L_i][4] arrays (offsets None) is packed."""
     if offsets is None:
@@ -442,6 +461,37 @@ class Context:
         """leaf updates of a device-resident node array of the ragged layout, enqueue only; d_work: [k][(arity + 1) * 4] u64 of scratch.
         An index >= n_leaves is ignored."""
         _lib.check(_lib.lib().pmx_merkle_ragged_update_dev(self._h, d_nodes, n_leaves, arity, d_indices, d_new_leaves, k, d_work, stream))
+
+    # ---- trees of a fixed depth: empty positions are default leaves, leaves are appended in place (host buffers only) ---
+    def merkle_fixed_defaults(self, default_leaf, arity: int, depth: int) -> np.ndarray:
+        """[depth + 1][4]: e[0] = default_leaf, e[l + 1] = the compression of `arity` copies of e[l] (pmx_merkle_fixed_defaults)"""
+        leaf = np.ascontiguousarray(default_leaf, dtype=np.uint64).reshape(4)
+        out = np.zeros((depth + 1, 4), dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_merkle_fixed_defaults(self._h, _ptr(leaf), arity, depth, _ptr(out)))
+        return out
+
+    def merkle_frontier_append(self, arity: int, depth: int, defaults, frontier, n_leaves: int, new_leaves, want_root: bool = True):
+        """(frontier [depth][arity - 1][4], root or None) after `new_leaves` [m][4] behind the n_leaves the frontier stands for
+        (pmx_merkle_frontier_append); frontier may be None iff n_leaves == 0."""
+        defaults = np.ascontiguousarray(defaults, dtype=np.uint64).reshape(depth + 1, 4)
+        new = np.ascontiguousarray(new_leaves, dtype=np.uint64).reshape(-1, 4)
+        if frontier is not None:
+            frontier = np.ascontiguousarray(frontier, dtype=np.uint64).reshape(depth, arity - 1, 4)
+        out = np.zeros((depth, arity - 1, 4), dtype=np.uint64)
+        root = np.zeros(4, dtype=np.uint64) if want_root else None
+        _lib.check(_lib.lib().pmx_merkle_frontier_append(self._h, arity, depth, _ptr(defaults), _ptr(frontier), n_leaves,
+                                                         _ptr(new) if new.shape[0] else None, new.shape[0], _ptr(out), _ptr(root)))
+        return out, root
+
+    def merkle_fixed(self, leaves, arity: int, depth: int, defaults, want_nodes: bool = True):
+        """(nodes, root) of the tree of `arity` and `depth` over leaves [n][4], n >= 1, every other position a default leaf
+        (pmx_merkle_fixed): nodes [n_nodes][4] as merkle_fixed_shape says, or None."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1, 4)
+        defaults = np.ascontiguousarray(defaults, dtype=np.uint64).reshape(depth + 1, 4)
+        nodes = np.zeros((merkle_fixed_shape(leaves.shape[0], arity, depth), 4), dtype=np.uint64) if want_nodes else None
+        root = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.lib().pmx_merkle_fixed(self._h, _ptr(leaves), leaves.shape[0], arity, depth, _ptr(defaults), _ptr(nodes), _ptr(root)))
+        return nodes, root
 
     # ---- matrix commitments: `matrix` is the flat element array [n_rows * row_len][4] in the given layout (a pointer-sized int: a raw
     # host address, page-locked memory of pmx_host_alloc for instance) ---------
