@@ -20,6 +20,7 @@
 #include "pmx_prepare.hpp"
 #include "pmx_launch.hpp"
 #include "pmx_grind_plan.hpp"
+#include "pmx_host_pieces.hpp"
 #include "pmx_matrix_shape.hpp"
 #include "pmx_sponge_plan.hpp"
 #include "pmx_squeeze_cut.hpp"
@@ -61,6 +62,15 @@ int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
 }
 
 }  // namespace pmx
+
+// The context's page-locked block, allocated on first use: what a host-buffer call of at most kSmallCallBytes stages through, one copy
+// each way (the caller holds host_lock).
+static constexpr size_t kSmallCallBytes = 64 * 1024;
+static int ctx_pinned(pmx_ctx *ctx, char **out) {
+    if (!ctx->pinned) PMX_HIP(hipHostMalloc(&ctx->pinned, kSmallCallBytes, hipHostMallocDefault));
+    *out = (char *)ctx->pinned;
+    return PMX_OK;
+}
 
 // The host-buffer pipeline of a batch whose buffers are page-locked: chunk i is uploaded on `stream`, computed on `stream2` behind the
 // upload's event and downloaded on `stream3` behind the kernel's - the two copy directions have a stream (and a DMA engine) each, so chunk
@@ -570,11 +580,8 @@ extern "C" int pmx_hash_batch(pmx_ctx *ctx, const uint64_t *in, size_t in_len, u
 
 // ---- duplex sponge driver ------------------------------------------------------------------------
 // The pass drivers launch one kernel per permutation a sponge of the call can need: a call is limited to kMaxPasses of them
-// (65536 rates of elements per sponge and call - 16 MiB at rate 8; longer inputs are absorbed in several calls, which is the same
-// thing to a duplex sponge).  The limit is the same for EVERY absorb and squeeze call, whichever engine the width and the batch
-// size select (the per-lane kernels loop inside one launch and would not need it: a caller's length limit must not depend on
-// its batch size).
-static constexpr size_t kMaxPasses = 65536;  // launches = permutations a sponge of the call can need
+// (pmx_host_pieces.hpp: 65536 rates of elements per sponge and call - 16 MiB at rate 8; longer inputs are absorbed in several calls,
+// which is the same thing to a duplex sponge).
 static int check_pass_count(const pmx_ctx *ctx, int op, size_t /*n*/, size_t len, const char *who) {
     const uint32_t rate = ctx->dev.rounds.rate;
     const size_t passes = rate == 0 ? 0 : (op == PMX_OP_SQUEEZE ? squeeze_passes(len, rate) : absorb_passes(len, rate));
@@ -669,8 +676,6 @@ extern "C" int pmx_sponge_squeeze_batch_dev(pmx_ctx *ctx, uint64_t *d_states, ui
     PMX_ABI_END
 }
 
-static constexpr size_t kSmallCallBytes = 64 * 1024;
-
 static int check_modes(const pmx_ctx *ctx, const uint32_t *tag, const uint32_t *index, size_t n) {
     for (size_t i = 0; i < n; ++i) {
         if (tag[i] > PMX_MODE_SQUEEZING) return set_error(PMX_ERR_ARG, "sponge %zu: mode tag %u is neither Absorbing nor Squeezing", i, tag[i]);
@@ -679,6 +684,57 @@ static int check_modes(const pmx_ctx *ctx, const uint32_t *tag, const uint32_t *
     return PMX_OK;
 }
 
+// n sponges resident on the device for the length of a host-buffer call: [states | tag | index] in staging slot 0, the mode words on
+// 16-byte boundaries.  The caller holds host_lock, drains the streams, and reads nothing back before its last piece is enqueued: a call
+// that fails half way leaves the caller's sponges as they were.
+struct ResidentSponges {
+    uint64_t *states = nullptr;
+    uint32_t *tag = nullptr, *index = nullptr;
+    size_t n = 0, st_bytes = 0, bytes = 0;
+
+    int place(pmx_ctx *ctx, size_t n_, size_t st_bytes_) {
+        const size_t words = (n_ * 4 + 15) / 16 * 16;
+        void *d = nullptr;
+        if (int rc = ctx_scratch(ctx, 0, st_bytes_ + 2 * words, &d)) return rc;
+        n = n_, st_bytes = st_bytes_, bytes = st_bytes_ + 2 * words;
+        states = (uint64_t *)d;
+        tag = (uint32_t *)((char *)d + st_bytes);
+        index = (uint32_t *)((char *)d + st_bytes + words);
+        return PMX_OK;
+    }
+    int upload(const uint64_t *h_states, const uint32_t *h_tag, const uint32_t *h_index, hipStream_t st) const {
+        PMX_HIP(hipMemcpyAsync(states, h_states, st_bytes, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(tag, h_tag, n * 4, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(index, h_index, n * 4, hipMemcpyHostToDevice, st));
+        return PMX_OK;
+    }
+    int fresh(hipStream_t st) const {   // zero state, Absorbing{0} (mod.rs:219-230)
+        PMX_HIP(hipMemsetAsync(states, 0, bytes, st));
+        return PMX_OK;
+    }
+    int download(uint64_t *h_states, uint32_t *h_tag, uint32_t *h_index, hipStream_t st) const {
+        PMX_HIP(hipMemcpyAsync(h_states, states, st_bytes, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(h_tag, tag, n * 4, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(h_index, index, n * 4, hipMemcpyDeviceToHost, st));
+        return PMX_OK;
+    }
+};
+
+// `width` bytes of each of n rows between the caller's rows (of its pitch) and a packed [n][width] device block: a piece's columns.
+// One row, or a piece as wide as the rows, is one contiguous copy.
+static int copy_columns(void *dst, size_t dst_pitch, const void *src, size_t src_pitch, size_t width, size_t n, hipMemcpyKind kind,
+                        hipStream_t st) {
+    if (width == 0) return PMX_OK;
+    if (n == 1 || (width == dst_pitch && width == src_pitch)) PMX_HIP(hipMemcpyAsync(dst, src, n * width, kind, st));
+    else PMX_HIP(hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, width, n, kind, st));
+    return PMX_OK;
+}
+
+// The host absorb and squeeze of field elements take any length, as the reference does (mod.rs:232-254, 321-341): a small call goes
+// through the context's page-locked block, every other call is the resident walk - the sponges up once, every piece of fixed_piece
+// (pmx_host_pieces.hpp; a call within kMaxPasses rates is its one piece) through the _dev entry on ctx->stream with its columns moved
+// up in front of it (absorb) or down behind it (squeeze), the sponges down once.  An error half way through a call of several pieces
+// leaves the caller's states and mode words untouched (a squeeze's `out` holds the pieces that were done).
 static int sponge_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in, uint64_t *out,
                        size_t len, size_t n, bool absorb) {
     PMX_ABI_BEGIN("pmx_sponge_*_batch")
@@ -688,45 +744,22 @@ static int sponge_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
     if ((absorb && !in) || (!absorb && !out && len)) return set_error(PMX_ERR_ARG, "pmx_sponge_*_batch: null data pointer");
     int rc = check_modes(ctx, tag, index, n);
     if (rc) return rc;
-    // The reference takes any length (mod.rs:232-254, 321-341); a device call moves at most kMaxPasses rates per sponge (check_pass_count).
-    // To a duplex sponge `absorb(a ++ b)` is `absorb(a); absorb(b)`, and `squeeze(k1 + k2)` is `squeeze(k1); squeeze(k2)` unless the
-    // second call asks for exactly `rate` elements from a sponge that stands inside its rate (the test of mod.rs:175 then skips a
-    // permutation the long call performs): a longer call is cut into pieces of kMaxPasses rates, never leaving a last piece of one rate.
     const size_t rate = ctx->dev.rounds.rate, max_len = kMaxPasses * rate;
-    if (rate != 0 && len > max_len) {
-        std::vector<uint64_t> rows;   // n > 1: the piece of every sponge, packed [n][piece]
-        for (size_t done = 0; done < len;) {
-            size_t piece = len - done < max_len ? len - done : max_len;
-            if (len - done - piece == rate) piece -= rate;   // (kMaxPasses > 1: the piece stays positive and is not `rate` itself)
-            const uint64_t *in_piece = in ? in + done * 4 : nullptr;
-            uint64_t *out_piece = out ? out + done * 4 : nullptr;
-            if (n > 1) {
-                if (n > (SIZE_MAX / 32) / piece) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
-                rows.resize(n * piece * 4);
-                if (absorb)
-                    for (size_t i = 0; i < n; ++i) std::memcpy(rows.data() + i * piece * 4, in + (i * len + done) * 4, piece * 32);
-                in_piece = out_piece = rows.data();
-            }
-            if ((rc = sponge_host(ctx, states, tag, index, absorb ? in_piece : nullptr, absorb ? nullptr : out_piece, piece, n, absorb))) return rc;
-            if (!absorb && n > 1)
-                for (size_t i = 0; i < n; ++i) std::memcpy(out + (i * len + done) * 4, rows.data() + i * piece * 4, piece * 32);
-            done += piece;
-        }
-        return PMX_OK;
-    }
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->host_lock);
-    size_t st_bytes = 0, io_bytes = 0;
-    if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(n, len, &io_bytes))) return rc;
+    size_t st_bytes = 0, io_bytes = 0;   // (io: the widest piece)
+    if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(n, std::min(len, max_len), &io_bytes))) return rc;
     // A handful of sponges (the single PoseidonSponge of the trait shims is n = 1): the call is all latency, and eight
     // separate copies from pageable memory cost as much as the permutation itself.  Pack [states | io | tag | index] into
-    // the context's page-locked block: one copy in, the kernel, one copy out.
+    // the context's page-locked block: one copy in, the kernel, one copy out.  (One sponge's max_len elements are 2 MiB and more:
+    // a call of several pieces never fits.)
     const size_t words = (n * 4 + 15) / 16 * 16, packed = st_bytes + io_bytes + 2 * words;
     if (packed <= kSmallCallBytes) {
-        if (!ctx->pinned) PMX_HIP(hipHostMalloc(&ctx->pinned, kSmallCallBytes, hipHostMallocDefault));
+        char *h = nullptr;
+        if ((rc = ctx_pinned(ctx, &h))) return rc;
         void *d = nullptr;
         if ((rc = ctx_scratch(ctx, 0, packed, &d))) return rc;
-        char *h = (char *)ctx->pinned, *dd = (char *)d;
+        char *dd = (char *)d;
         const size_t o_io = st_bytes, o_tag = st_bytes + io_bytes, o_idx = o_tag + words;
         std::memcpy(h, states, st_bytes);
         if (absorb) std::memcpy(h + o_io, in, io_bytes);
@@ -745,27 +778,28 @@ static int sponge_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
         if (!absorb && io_bytes) std::memcpy(out, h + o_io, io_bytes);
         return PMX_OK;
     }
-    void *d_st = nullptr, *d_io = nullptr, *d_tag = nullptr, *d_idx = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, st_bytes, &d_st))) return rc;
+    ResidentSponges sp;
+    void *d_io = nullptr;   // slot 1: the piece's columns, packed [n][piece]
+    if ((rc = sp.place(ctx, n, st_bytes))) return rc;
     if ((rc = ctx_scratch(ctx, 1, io_bytes, &d_io))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, n * 4, &d_tag))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, n * 4, &d_idx))) return rc;
     StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d_st, states, st_bytes, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_tag, tag, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_idx, index, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (absorb) {
-        PMX_HIP(hipMemcpyAsync(d_io, in, io_bytes, hipMemcpyHostToDevice, ctx->stream));
-        rc = pmx_sponge_absorb_batch_dev(ctx, (uint64_t *)d_st, (uint32_t *)d_tag, (uint32_t *)d_idx, (const uint64_t *)d_io, len, n, ctx->stream);
-    } else {
-        rc = pmx_sponge_squeeze_batch_dev(ctx, (uint64_t *)d_st, (uint32_t *)d_tag, (uint32_t *)d_idx, (uint64_t *)d_io, len, n, ctx->stream);
-    }
-    if (rc) return rc;
-    PMX_HIP(hipMemcpyAsync(states, d_st, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(tag, d_tag, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(index, d_idx, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (!absorb && io_bytes) PMX_HIP(hipMemcpyAsync(out, d_io, io_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    hipStream_t st = ctx->stream;
+    if ((rc = sp.upload(states, tag, index, st))) return rc;
+    size_t done = 0;   // elements per sponge so far
+    do {
+        const size_t piece = fixed_piece(done, len, max_len, rate);
+        if (absorb) {
+            if ((rc = copy_columns(d_io, piece * 32, in + done * 4, len * 32, piece * 32, n, hipMemcpyHostToDevice, st))) return rc;
+            rc = pmx_sponge_absorb_batch_dev(ctx, sp.states, sp.tag, sp.index, (const uint64_t *)d_io, piece, n, st);
+        } else {
+            rc = pmx_sponge_squeeze_batch_dev(ctx, sp.states, sp.tag, sp.index, (uint64_t *)d_io, piece, n, st);
+            if (!rc) rc = copy_columns(out + done * 4, len * 32, d_io, piece * 32, piece * 32, n, hipMemcpyDeviceToHost, st);
+        }
+        if (rc) return rc;
+        done += piece;
+    } while (done < len);
+    if ((rc = sp.download(states, tag, index, st))) return rc;
+    PMX_HIP(hipStreamSynchronize(st));
     return PMX_OK;
     PMX_ABI_END
 }
@@ -812,9 +846,9 @@ extern "C" int pmx_sponge_squeeze_bits_batch_dev(pmx_ctx *ctx, uint64_t *d_state
     return squeeze_cut_dev(ctx, d_states, d_mode_tag, d_mode_index, d_out, num_bits, n, stream, true, "pmx_sponge_squeeze_bits_batch_dev");
 }
 
-// Host buffers: states and mode words go up once and stay on the device; a call beyond kMaxPasses rates of elements is cut on element
-// boundaries with the rule of sponge_host (never a last piece of exactly one rate, mod.rs:175), the truncation falls into the last piece,
-// and every piece's [n][piece] block comes down into its columns of the caller's rows: n * len bytes over the link in all.
+// Host buffers: the resident walk of sponge_host, in native elements - a call beyond kMaxPasses rates of them is cut on element
+// boundaries by fixed_piece (pmx_host_pieces.hpp), the truncation falls into the last piece, and every piece's [n][piece] block comes
+// down into its columns of the caller's rows: n * len bytes over the link in all.
 static int squeeze_cut_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *index, uint8_t *out, size_t len, size_t n, bool bits,
                             const char *who) {
     PMX_ABI_BEGIN(who)
@@ -831,29 +865,22 @@ static int squeeze_cut_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint3
     const size_t widest = std::min(len, max_elems * unit);   // output units of the longest piece
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->host_lock);
-    void *d_st = nullptr, *d_io = nullptr, *d_tag = nullptr, *d_idx = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, st_bytes, &d_st))) return rc;
+    ResidentSponges sp;
+    void *d_io = nullptr;
+    if ((rc = sp.place(ctx, n, st_bytes))) return rc;
     if ((rc = ctx_scratch(ctx, 1, n * widest, &d_io))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, n * 4, &d_tag))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, n * 4, &d_idx))) return rc;
     StreamDrain drain{ctx};
     hipStream_t st = ctx->stream;
-    PMX_HIP(hipMemcpyAsync(d_st, states, st_bytes, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(d_tag, tag, n * 4, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(d_idx, index, n * 4, hipMemcpyHostToDevice, st));
+    if ((rc = sp.upload(states, tag, index, st))) return rc;
     size_t done = 0;   // elements squeezed so far
     do {
-        size_t piece = elems - done < max_elems ? elems - done : max_elems;
-        if (elems - done - piece == rate) piece -= rate;   // (kMaxPasses > 1: the piece stays positive and is not `rate` itself)
+        const size_t piece = fixed_piece(done, elems, max_elems, rate);
         const size_t col = done * unit, width = std::min(len - col, piece * unit);
-        if ((rc = squeeze_cut_dev(ctx, (uint64_t *)d_st, (uint32_t *)d_tag, (uint32_t *)d_idx, (uint8_t *)d_io, width, n, st, bits, who))) return rc;
-        if (width == len && len) PMX_HIP(hipMemcpyAsync(out, d_io, n * len, hipMemcpyDeviceToHost, st));
-        else if (width) PMX_HIP(hipMemcpy2DAsync(out + col, len, d_io, width, width, n, hipMemcpyDeviceToHost, st));
+        if ((rc = squeeze_cut_dev(ctx, sp.states, sp.tag, sp.index, (uint8_t *)d_io, width, n, st, bits, who))) return rc;
+        if ((rc = copy_columns(out + col, len, d_io, width, width, n, hipMemcpyDeviceToHost, st))) return rc;
         done += piece;
     } while (done < elems);
-    PMX_HIP(hipMemcpyAsync(states, d_st, st_bytes, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(tag, d_tag, n * 4, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(index, d_idx, n * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = sp.download(states, tag, index, st))) return rc;
     PMX_HIP(hipStreamSynchronize(st));
     return PMX_OK;
     PMX_ABI_END
@@ -896,10 +923,10 @@ extern "C" int pmx_sponge_grind(pmx_ctx *ctx, const uint64_t *state, uint32_t mo
     std::lock_guard<std::mutex> lock(ctx->host_lock);
     // staging: [state t x 32 bytes | the smallest accepted nonce | whether there is one], one copy up, 16 bytes down per chunk
     const size_t st_bytes = (size_t)ctx->t * 32;
-    if (!ctx->pinned) PMX_HIP(hipHostMalloc(&ctx->pinned, kSmallCallBytes, hipHostMallocDefault));
+    char *h = nullptr;
+    if ((rc = ctx_pinned(ctx, &h))) return rc;
     void *d = nullptr;
     if ((rc = ctx_scratch(ctx, 0, st_bytes + 16, &d))) return rc;
-    char *h = (char *)ctx->pinned;
     uint64_t *h_res = (uint64_t *)(h + st_bytes), *d_state = (uint64_t *)d, *d_res = (uint64_t *)((char *)d + st_bytes);
     std::memcpy(h, state, st_bytes);
     h_res[0] = UINT64_MAX;
@@ -990,62 +1017,48 @@ static int varlen_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
     if (total == 0 && !hash) return PMX_OK;   // every row empty: nothing changes (mod.rs:234-236)
     size_t longest = 0;
     for (size_t i = 0; i < n; ++i) longest = std::max<size_t>(longest, offsets[i + 1] - offsets[i]);
-    const size_t piece = kMaxPasses * ctx->dev.rounds.rate, pieces = longest == 0 ? 0 : (longest + piece - 1) / piece;
+    const size_t piece = kMaxPasses * ctx->dev.rounds.rate, pieces = ragged_pieces(longest, piece);
     size_t st_bytes = 0, in_bytes = 0, out_bytes = 0;
     if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(total, 1, &in_bytes)) || (rc = batch_bytes(n, hash ? out_len : 0, &out_bytes)))
         return rc;
     if (hash && (rc = check_pass_count(ctx, PMX_OP_SQUEEZE, n, out_len, who))) return rc;
     PMX_BIND(ctx);
     std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: [states | tag | index] of the n sponges; slot 1: the input (or one piece of it); slot 2: the offsets; slot 3: the digests
-    const size_t words = (n * 4 + 15) / 16 * 16;
-    void *d_sp = nullptr, *d_in = nullptr, *d_off = nullptr, *d_out = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, st_bytes + 2 * words, &d_sp))) return rc;
+    // slot 0: the n resident sponges; slot 1: the input (or one piece of it); slot 2: the offsets; slot 3: the digests
+    ResidentSponges sp;
+    void *d_in = nullptr, *d_off = nullptr, *d_out = nullptr;
+    if ((rc = sp.place(ctx, n, st_bytes))) return rc;
     if ((rc = ctx_scratch(ctx, 1, pieces > 1 ? std::min(in_bytes, n * piece * 32) : in_bytes, &d_in))) return rc;
     if ((rc = ctx_scratch(ctx, 2, (n + 1) * 8, &d_off))) return rc;
     if (hash && (rc = ctx_scratch(ctx, 3, out_bytes, &d_out))) return rc;
-    uint64_t *d_st = (uint64_t *)d_sp;
-    uint32_t *d_tag = (uint32_t *)((char *)d_sp + st_bytes), *d_idx = (uint32_t *)((char *)d_sp + st_bytes + words);
     StreamDrain drain{ctx};
     hipStream_t st = ctx->stream;
-    if (hash) {
-        PMX_HIP(hipMemsetAsync(d_sp, 0, st_bytes + 2 * words, st));   // n fresh sponges: zero state, Absorbing{0} (mod.rs:219-230)
-    } else {
-        PMX_HIP(hipMemcpyAsync(d_st, states, st_bytes, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_tag, tag, n * 4, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_idx, index, n * 4, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = hash ? sp.fresh(st) : sp.upload(states, tag, index, st))) return rc;
     std::vector<uint64_t> off(n + 1), packed;
     for (size_t k = 0; k < pieces; ++k) {
-        // piece k of row i: elements [k * piece, (k + 1) * piece) of the row, rebased so that the uploaded input starts at offset 0
+        // piece k of every row (ragged_range), rebased so that the uploaded input starts at offset 0
         const uint64_t *src = in + offsets[0] * 4;
-        off[0] = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const size_t len = offsets[i + 1] - offsets[i], lo = std::min(len, k * piece), hi = std::min(len, (k + 1) * piece);
-            off[i + 1] = pieces == 1 ? offsets[i + 1] - offsets[0] : off[i] + (hi - lo);
-        }
+        ragged_offsets(offsets, n, piece, k, off.data());
         if (pieces > 1) {
             packed.resize(off[n] * 4);
             for (size_t i = 0; i < n; ++i) {
-                const size_t len = offsets[i + 1] - offsets[i], lo = std::min(len, k * piece);
+                const size_t lo = ragged_range(offsets[i + 1] - offsets[i], piece, k).lo;
                 if (off[i + 1] > off[i]) std::memcpy(packed.data() + off[i] * 4, in + (offsets[i] + lo) * 4, (off[i + 1] - off[i]) * 32);
             }
             src = packed.data();
         }
         if (off[n]) PMX_HIP(hipMemcpyAsync(d_in, src, off[n] * 32, hipMemcpyHostToDevice, st));
         PMX_HIP(hipMemcpyAsync(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-        if ((rc = pmx_sponge_absorb_varlen_batch_dev(ctx, d_st, d_tag, d_idx, (const uint64_t *)d_in, (const uint64_t *)d_off,
+        if ((rc = pmx_sponge_absorb_varlen_batch_dev(ctx, sp.states, sp.tag, sp.index, (const uint64_t *)d_in, (const uint64_t *)d_off,
                                                      std::min(longest, piece), n, st)))
             return rc;
         PMX_HIP(hipStreamSynchronize(st));   // (`off` and `packed` are rewritten for the next piece)
     }
     if (hash) {
-        if ((rc = pmx_sponge_squeeze_batch_dev(ctx, d_st, d_tag, d_idx, (uint64_t *)d_out, out_len, n, st))) return rc;
+        if ((rc = pmx_sponge_squeeze_batch_dev(ctx, sp.states, sp.tag, sp.index, (uint64_t *)d_out, out_len, n, st))) return rc;
         PMX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    } else {
-        PMX_HIP(hipMemcpyAsync(states, d_st, st_bytes, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(tag, d_tag, n * 4, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(index, d_idx, n * 4, hipMemcpyDeviceToHost, st));
+    } else if ((rc = sp.download(states, tag, index, st))) {
+        return rc;
     }
     PMX_HIP(hipStreamSynchronize(st));
     return PMX_OK;
@@ -1140,9 +1153,10 @@ int matrix_host(pmx_ctx *ctx, const uint64_t *matrix, size_t n_rows, size_t row_
     const char *src = (const char *)matrix;
     const bool small = bytes <= kSmallCallBytes && !is_pinned(matrix);
     if (small) {
-        if (!ctx->pinned) PMX_HIP(hipHostMalloc(&ctx->pinned, kSmallCallBytes, hipHostMallocDefault));
-        std::memcpy(ctx->pinned, matrix, (size_t)bytes);
-        src = (const char *)ctx->pinned;
+        char *h = nullptr;
+        if ((rc = ctx_pinned(ctx, &h))) return rc;
+        std::memcpy(h, matrix, (size_t)bytes);
+        src = h;
     }
     ScopedPin pin(small ? nullptr : matrix, (size_t)bytes);   // (in front of the drain: see pmx_permute_batch)
     StreamDrain drain{ctx};

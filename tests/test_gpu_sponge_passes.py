@@ -228,6 +228,44 @@ def test_host_calls_longer_than_65536_rates_are_cut_into_pieces_the_reference_ta
             assert np.array_equal(batch.state[j], s2) and (int(batch.mode_tag[j]), int(batch.mode_index[j])) == (m2, i2), ("squeeze", n, j)
 
 
+def test_host_calls_on_both_sides_of_the_packed_path_agree_with_the_c_oracle_and_each_other():
+    """The host entries stage a call of at most 64 KiB - [states | io | tag | index], the mode words padded to 16 bytes - through the
+    context's page-locked block with one copy each way, and run every larger call as the resident walk (pmx_api.cpp: sponge_host,
+    kSmallCallBytes).  t = 3, rate 2, mixed modes, absorb(4) then squeeze(3) through the host entries: 2100 sponges (far past the
+    switch) and 500 (112 000 bytes for the absorb, 104 000 for the squeeze: past it too, though nearer), and the batch sizes on either
+    side of the switch itself - absorb(4) packs up to 282 sponges (65 440 bytes; 283: 65 664), squeeze(3) up to 327 (65 408; 328:
+    65 600) - so 282 runs both calls packed, 283 the absorb resident and the squeeze packed, 328 both resident.  Every sponge of every
+    call against the C restatement, and the calls against each other on the sponges they share."""
+    f, cfg, cr = _config("bls12_381_fr", None, 255, 2, 5, 8, 31)
+    r, t, big = 2, 3, 2100
+
+    def packed(n, length):
+        return n * t * 32 + n * length * 32 + 2 * ((n * 4 + 15) // 16 * 16)
+    assert packed(282, 4) <= 65536 < packed(283, 4) and packed(327, 3) <= 65536 < packed(328, 3) and packed(500, 3) > 65536
+
+    rng = np.random.default_rng(0x5CA1E)
+    state0 = synth.random_elements(f, big * t, seed=71).reshape(big, t, 4)
+    tag0, idx0 = _modes(big, r, "random", rng)
+    elems = synth.random_elements(f, big * 4, seed=72).reshape(big, 4, 4)
+    want = cr.sponge_absorb_each(state0, tag0, idx0, elems, np.arange(big + 1) * 4)
+    want_absorbed = tuple(a.copy() for a in want)
+    want_st, want_tag, want_idx, want_out = cr.sponge_squeeze_each(*want, 3)
+    runs = {}
+    for n in (big, 500, 328, 283, 282):
+        b = S.BatchPoseidonSponge.new(cfg, n)
+        b.state, b.mode_tag, b.mode_index = state0[:n].copy(), tag0[:n].copy(), idx0[:n].copy()
+        b.absorb(np.ascontiguousarray(elems[:n]))
+        for got, ref in zip((b.state, b.mode_tag, b.mode_index), want_absorbed):
+            assert np.array_equal(got, ref[:n]), ("absorb", n, np.nonzero((np.asarray(got) != ref[:n]).reshape(n, -1).any(axis=1))[0][:8])
+        out = b.squeeze_native_field_elements(3)
+        for got, ref in zip((out, b.state, b.mode_tag, b.mode_index), (want_out, want_st, want_tag, want_idx)):
+            assert np.array_equal(got, ref[:n]), ("squeeze", n, np.nonzero((np.asarray(got) != ref[:n]).reshape(n, -1).any(axis=1))[0][:8])
+        runs[n] = (out, b.state.copy(), b.mode_tag.copy(), b.mode_index.copy())
+    for n in (500, 328, 283, 282):      # the same sponges through the other path: limb for limb what the large call gave them
+        for a, b_ in zip(runs[big], runs[n]):
+            assert np.array_equal(a[:n], b_)
+
+
 @pytest.mark.parametrize("name", ["bls_t3_a5_8_31", "bls_t3_a17_8_31", "bls_t3_a257_8_13"])
 def test_t3_calls_above_the_quad_range_run_on_the_matrix_core_engine_and_agree_with_the_quad_kernels(name):
     """t = 3 - alpha = 5 (BASELINE configs[1]'s shape), alpha = 17 (the reference's own rate-2 default and the config of its only

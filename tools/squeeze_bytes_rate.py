@@ -167,7 +167,9 @@ def run(label, field, p, bits, rate, log_n, seed):
                 first = outs[name]
                 assert np.array_equal(first[sample], cut_bytes(p, want_el, 32, False)), (label, name)
     res.update({"host_native_then_from_mont_then_cut_ms": round(float(np.median(times["before"])), 3),
+                "host_native_then_from_mont_then_cut_ms_min_max": [round(min(times["before"]), 3), round(max(times["before"]), 3)],
                 "host_squeeze_bytes_ms": round(float(np.median(times["after"])), 3),
+                "host_squeeze_bytes_ms_min_max": [round(min(times["after"]), 3), round(max(times["after"]), 3)],
                 "host_speedup": round(float(np.median(times["before"]) / np.median(times["after"])), 2)})
     return res
 
