@@ -155,12 +155,9 @@ hipError_t launch_squeeze_cut(const DevConfig &c, uint32_t t, uint64_t *states, 
         if (e != hipSuccess) break;
         const uint64_t total = (uint64_t)cnt * elems;
         uint8_t *dst = out + first * len;
-        if (bits)
-            hipLaunchKernelGGL(squeeze_bits_kernel, dim3((unsigned)((total + kBitElems - 1) / kBitElems)), dim3(kCutThreads), 0, st, block, dst, f,
-                               total, (uint32_t)elems, (uint64_t)len, unit);
-        else
-            hipLaunchKernelGGL(squeeze_bytes_kernel, dim3((unsigned)((total + kByteElems - 1) / kByteElems)), dim3(kCutThreads), 0, st, block, dst, f,
-                               total, (uint32_t)elems, (uint64_t)len, unit);
+        const uint32_t group = bits ? kBitElems : kByteElems;   // elements per workgroup
+        hipLaunchKernelGGL(bits ? squeeze_bits_kernel : squeeze_bytes_kernel, dim3((unsigned)((total + group - 1) / group)), dim3(kCutThreads), 0, st,
+                           block, dst, f, total, (uint32_t)elems, (uint64_t)len, unit);
         e = hipGetLastError();
     }
     scratch.done(scratch.owner, st, block);

@@ -165,23 +165,17 @@ struct HybridEngine : LanePerUnit<64 * kMfmaWaves> {
             return a;
         }
     };
-    __device__ __forceinline__ void load_states(const uint64_t *g_states, size_t n) {
+    template <class Adjust = NoAdjust>
+    __device__ __forceinline__ void load_states(const uint64_t *g_states, size_t n, const Adjust &adjust = Adjust{}) {
         const size_t gid = (size_t)blockIdx.x * kThreads + threadIdx.x;
-        load_elements(reinterpret_cast<const uint4 *>(g_states) + (gid < n ? gid : 0) * kChunks, NoAdjust{});
-    }
-    __device__ __forceinline__ void load_states(const uint64_t *g_states, size_t n, const AbsorbAdjust &add) {
-        const size_t gid = (size_t)blockIdx.x * kThreads + threadIdx.x;
-        load_elements(reinterpret_cast<const uint4 *>(g_states) + (gid < n ? gid : 0) * kChunks, add);
+        load_elements(reinterpret_cast<const uint4 *>(g_states) + (gid < n ? gid : 0) * kChunks, adjust);
     }
 
     // the store goes through the wave's LDS region so that every 16-byte write instruction covers 1 KiB of contiguous memory:
     // written lane by lane (stride 32 T bytes) the partial lines are not all merged before they leave the L2 - 1.57 x the
     // bytes at t = 9 (WRITE_SIZE, profiles/r03)
-    __device__ __forceinline__ void store_states(uint64_t *g_states, size_t n) {
-        const size_t first = (size_t)blockIdx.x * kThreads + (threadIdx.x & ~63u);
-        const size_t valid = n > first ? (n - first < (size_t)64 ? n - first : (size_t)64) : 0;
-        uint4 *g = reinterpret_cast<uint4 *>(g_states) + first * kChunks;
-        const uint32_t n_chunks = (uint32_t)valid * kChunks;
+    // (the T exact reductions of a store, once, into the wave's region, between two workgroup barriers)
+    __device__ __forceinline__ void stage_abi() {
         __syncthreads();
         static_for<0, T>([&](auto i) {
             const Abi a = to_abi(s[i]);
@@ -190,10 +184,24 @@ struct HybridEngine : LanePerUnit<64 * kMfmaWaves> {
             PMX_SCHED_FENCE();   // one conversion at a time: interleaved, the T exact reductions are the widest point of the kernel
         });
         __syncthreads();
+    }
+    // this wave's 64 consecutive states of a batch of n: where their chunks start, and how many of them exist
+    struct WaveSpan {
+        uint4 *g;
+        uint32_t n_chunks;
+    };
+    __device__ __forceinline__ static WaveSpan wave_span(uint64_t *g_states, size_t n) {
+        const size_t first = (size_t)blockIdx.x * kThreads + (threadIdx.x & ~63u);
+        const size_t valid = n > first ? (n - first < (size_t)64 ? n - first : (size_t)64) : 0;
+        return WaveSpan{reinterpret_cast<uint4 *>(g_states) + first * kChunks, (uint32_t)valid * kChunks};
+    }
+    __device__ __forceinline__ void store_states(uint64_t *g_states, size_t n) {
+        const WaveSpan w = wave_span(g_states, n);
+        stage_abi();
 #pragma unroll
         for (int k = 0; k < kChunks; ++k) {
             const uint32_t q = lane + k * 64;
-            if (q < n_chunks) g[q] = region[q];
+            if (q < w.n_chunks) w.g[q] = region[q];
         }
         __syncthreads();
     }
@@ -221,22 +229,12 @@ struct HybridEngine : LanePerUnit<64 * kMfmaWaves> {
         }
     }
     __device__ __forceinline__ void store_states_where(uint64_t *g_states, size_t n, uint64_t keep_mask, const CopyOut &out) {
-        const size_t first = (size_t)blockIdx.x * kThreads + (threadIdx.x & ~63u);
-        const size_t valid = n > first ? (n - first < (size_t)64 ? n - first : (size_t)64) : 0;
-        uint4 *g = reinterpret_cast<uint4 *>(g_states) + first * kChunks;
-        const uint32_t n_chunks = (uint32_t)valid * kChunks;
-        __syncthreads();
-        static_for<0, T>([&](auto i) {
-            const Abi a = to_abi(s[i]);
-            region[lane * kChunks + 2 * i] = abi_lo(a);
-            region[lane * kChunks + 2 * i + 1] = abi_hi(a);
-            PMX_SCHED_FENCE();
-        });
-        __syncthreads();
+        const WaveSpan w = wave_span(g_states, n);
+        stage_abi();
 #pragma unroll
         for (int k = 0; k < kChunks; ++k) {
             const uint32_t q = lane + k * 64;
-            if (q < n_chunks && ((keep_mask >> (q / kChunks)) & 1)) g[q] = region[q];
+            if (q < w.n_chunks && ((keep_mask >> (q / kChunks)) & 1)) w.g[q] = region[q];
         }
         copy_out_staged(out);
         __syncthreads();
@@ -246,14 +244,7 @@ struct HybridEngine : LanePerUnit<64 * kMfmaWaves> {
     // wave's span goes out as whole kilobytes like store_states does; otherwise every lane writes its own state.  Either
     // way the T exact reductions happen once, into the wave's LDS region.
     __device__ __forceinline__ void store_state_at(uint64_t *mine, bool keep, bool together, uint64_t *wave_base, uint32_t valid, const CopyOut &out) {
-        __syncthreads();
-        static_for<0, T>([&](auto i) {
-            const Abi a = to_abi(s[i]);
-            region[lane * kChunks + 2 * i] = abi_lo(a);
-            region[lane * kChunks + 2 * i + 1] = abi_hi(a);
-            PMX_SCHED_FENCE();   // one conversion at a time (see store_states)
-        });
-        __syncthreads();
+        stage_abi();
         if (together) {          // wave-uniform
             uint4 *g = reinterpret_cast<uint4 *>(wave_base);
             const uint32_t n_chunks = valid * kChunks;
@@ -1158,57 +1149,40 @@ __global__ void __launch_bounds__(Engine::kThreads, Engine::kMinWaves)
 template <class Engine>
 struct Launch {
     static int grid(size_t n) { return (int)((n + Engine::kUnits - 1) / Engine::kUnits); }
-    // more than 64 KiB of dynamic LDS has to be asked for per kernel (and device)
-    template <class K>
-    static void allow_lds(K kernel, size_t bytes) {
-        if (bytes > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    // THE launch of an engine kernel, whichever: n units on `st` with the engine's workgroup and dynamic LDS; every kernel takes the config
+    // and its constants first.  More than 64 KiB of dynamic LDS has to be asked for per kernel (and device).
+    template <class K, class... A>
+    static hipError_t enqueue(K kernel, const DevConfig &c, uint32_t t, size_t n, hipStream_t st, A... args) {
+        const size_t lds = Engine::lds_bytes(c, t);
+        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(grid(n)), dim3(Engine::kThreads), lds, st, c, c.consts, args...);
+        return hipGetLastError();
     }
 
     static hipError_t permute(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st) {
-        allow_lds(permute_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(permute_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, states, n);
-        return hipGetLastError();
+        return enqueue(permute_kernel<Engine>, c, t, n, st, states, n);
     }
     static hipError_t hash(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out,
                            size_t out_len, size_t n, hipStream_t st) {
-        allow_lds(hash_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(hash_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, in, in_len, out, out_len, n);
-        return hipGetLastError();
+        return enqueue(hash_kernel<Engine>, c, t, n, st, in, in_len, out, out_len, n);
     }
     static hipError_t hash_strided(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, size_t row_stride, size_t elem_stride,
                                    uint64_t *out, size_t out_len, size_t n, hipStream_t st) {
-        allow_lds(hash_strided_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(hash_strided_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, in, in_len, row_stride, elem_stride, out, out_len, n);
-        return hipGetLastError();
+        return enqueue(hash_strided_kernel<Engine>, c, t, n, st, in, in_len, row_stride, elem_stride, out, out_len, n);
     }
     static hipError_t compress(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, size_t n, hipStream_t st) {
-        allow_lds(compress_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(compress_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, in, out, n);
-        return hipGetLastError();
+        return enqueue(compress_kernel<Engine>, c, t, n, st, in, out, n);
     }
     static hipError_t compress_ary(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n, hipStream_t st) {
-        allow_lds(compress_ary_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(compress_ary_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, in, arity, out, n);
-        return hipGetLastError();
+        return enqueue(compress_ary_kernel<Engine>, c, t, n, st, in, arity, out, n);
     }
     static hipError_t compress_ary_bounded(const DevConfig &c, uint32_t t, const uint64_t *in, uint64_t *out, uint32_t arity, size_t n_children,
                                            size_t n, hipStream_t st) {
-        allow_lds(compress_ary_bounded_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(compress_ary_bounded_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, in, arity, n_children, out, n);
-        return hipGetLastError();
+        return enqueue(compress_ary_bounded_kernel<Engine>, c, t, n, st, in, arity, n_children, out, n);
     }
     static hipError_t grind(const DevConfig &c, uint32_t t, const uint64_t *base, uint32_t index, uint32_t bits, uint64_t first, size_t n,
                             uint64_t *best, hipStream_t st) {
-        allow_lds(grind_kernel<Engine>, Engine::lds_bytes(c, t));
-        hipLaunchKernelGGL(grind_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                           c.consts, base, index, bits, first, n, best);
-        return hipGetLastError();
+        return enqueue(grind_kernel<Engine>, c, t, n, st, base, index, bits, first, n, best);
     }
     // absorb / squeeze: per-lane kernels, or - on an engine whose permutation must stay wave-uniform - passes on its permutation
     // (pmx_sponge_plan.hpp).  Only the form the engine has is instantiated.
@@ -1219,9 +1193,7 @@ struct Launch {
             uint64_t *io = const_cast<uint64_t *>(in);   // (the absorb form of the pass kernels only reads `io`)
             return sponge_passes<false>(c, t, states, tag, index, io, rows, n, st, scratch);
         } else {
-            hipLaunchKernelGGL((absorb_kernel<Engine, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                               c.consts, states, tag, index, in, rows, n);
-            return hipGetLastError();
+            return enqueue(absorb_kernel<Engine, Rows>, c, t, n, st, states, tag, index, in, rows, n);
         }
     }
     static hipError_t absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
@@ -1237,9 +1209,7 @@ struct Launch {
         if constexpr (Engine::kWaveUniformOnly) {
             return sponge_passes<true>(c, t, states, tag, index, out, RowsFixed{out_len}, n, st, scratch);
         } else {
-            hipLaunchKernelGGL(squeeze_kernel<Engine>, dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                               c.consts, states, tag, index, out, out_len, n);
-            return hipGetLastError();
+            return enqueue(squeeze_kernel<Engine>, c, t, n, st, states, tag, index, out, out_len, n);
         }
     }
     // the whole absorb / squeeze call as passes (pmx_sponge_plan.hpp): pass 0 over the batch, then one launch per further
@@ -1253,8 +1223,6 @@ struct Launch {
         const size_t passes = SQUEEZE ? squeeze_passes(len, c.rounds.rate) : absorb_passes(len, c.rounds.rate);
         if (passes == 0 || n == 0) return hipSuccess;
         if (n > 0xffffffffull || len > kSpongeMaxLen) return hipErrorInvalidValue;
-        allow_lds(permute_listed_kernel<Engine, SQUEEZE, Rows>, Engine::lds_bytes(c, t));
-        allow_lds(sponge_first_kernel<Engine, SQUEEZE, Rows>, Engine::lds_bytes(c, t));
         const uint32_t last = (uint32_t)(passes - 1);    // (no sponge permutes in the last pass)
         const size_t launches = pass_launches(passes);
         uint32_t *scratch = nullptr;                     // [counters, padded to 64 words | list A: n | list B: n]
@@ -1271,16 +1239,12 @@ struct Launch {
             lists[1] = scratch + head + n;
             e = hipMemsetAsync(scratch, 0, head * 4, st);
         }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((sponge_first_kernel<Engine, SQUEEZE, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c, c.consts,
-                               states, tag, index, io, rows, n, last, lists[1], scratch ? scratch + 1 : nullptr);
-            e = hipGetLastError();
-        }
-        for (uint32_t p = 1; p < launches && e == hipSuccess; ++p) {
-            hipLaunchKernelGGL((permute_listed_kernel<Engine, SQUEEZE, Rows>), dim3(grid(n)), dim3(Engine::kThreads), Engine::lds_bytes(c, t), st, c,
-                               c.consts, states, tag, index, io, rows, p, last, lists[p & 1], scratch + p, lists[(p + 1) & 1], scratch + p + 1);
-            e = hipGetLastError();
-        }
+        // (named listed kernel first: the kernels of a code object lie in the order the source names them, and that order is kept)
+        const auto listed = permute_listed_kernel<Engine, SQUEEZE, Rows>;
+        const auto first = sponge_first_kernel<Engine, SQUEEZE, Rows>;
+        if (e == hipSuccess) e = enqueue(first, c, t, n, st, states, tag, index, io, rows, n, last, lists[1], scratch ? scratch + 1 : nullptr);
+        for (uint32_t p = 1; p < launches && e == hipSuccess; ++p)
+            e = enqueue(listed, c, t, n, st, states, tag, index, io, rows, p, last, lists[p & 1], scratch + p, lists[(p + 1) & 1], scratch + p + 1);
         if (scratch && provider.done) provider.done(provider.owner, st, scratch);   // behind the last launch that reads the lists
         return e;
     }
@@ -1635,30 +1599,32 @@ __global__ void __launch_bounds__(256) node_children_bounded_kernel(const uint4 
     rows[gid] = v;
 }
 
+// THE launch of a data-movement kernel, whichever: one lane per 16-byte piece it writes (path_check_kernel: per path), 256 lanes a
+// workgroup, no LDS.  The elements of the callers' uint64_t arrays reach the kernels as their 16-byte halves (u4).
+static const uint4 *u4(const uint64_t *p) { return reinterpret_cast<const uint4 *>(p); }
+static uint4 *u4(uint64_t *p) { return reinterpret_cast<uint4 *>(p); }
+template <class K, class... A>
+static hipError_t plain(K kernel, size_t lanes, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, args...);
+    return hipGetLastError();
+}
+
 hipError_t launch_paths_gather_ragged(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices,
                                       uint64_t *paths, size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(paths_gather_ragged_kernel, dim3((unsigned)((k * depth * 2 * (arity - 1) + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4 *>(nodes), (uint64_t)n_leaves, arity, depth, indices, reinterpret_cast<uint4 *>(paths), k);
-    return hipGetLastError();
+    return plain(paths_gather_ragged_kernel, k * depth * 2 * (arity - 1), st, u4(nodes), n_leaves, arity, depth, indices, u4(paths), k);
 }
 hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first,
                                         uint64_t width, uint32_t arity, uint64_t *rows, size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(node_children_bounded_kernel, dim3((unsigned)((k * 2 * arity + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4 *>(nodes), indices, pow, n_leaves, first, width, arity, reinterpret_cast<uint4 *>(rows), k);
-    return hipGetLastError();
+    return plain(node_children_bounded_kernel, k * 2 * arity, st, u4(nodes), indices, pow, n_leaves, first, width, arity, u4(rows), k);
 }
 
 hipError_t launch_node_scatter(const uint64_t *src, const uint64_t *indices, uint64_t pow, uint64_t limit, uint64_t base, uint64_t *dst,
                                size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)((k * 2 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(src),
-                       indices, pow, limit, base, reinterpret_cast<uint4 *>(dst), k);
-    return hipGetLastError();
+    return plain(node_scatter_kernel, k * 2, st, u4(src), indices, pow, limit, base, u4(dst), k);
 }
 hipError_t launch_node_children(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first, uint32_t arity,
                                 uint64_t *rows, size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(node_children_kernel, dim3((unsigned)((k * 2 * arity + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4 *>(nodes), indices, pow, n_leaves, first, arity, reinterpret_cast<uint4 *>(rows), k);
-    return hipGetLastError();
+    return plain(node_children_kernel, k * 2 * arity, st, u4(nodes), indices, pow, n_leaves, first, arity, u4(rows), k);
 }
 
 // ---- fixed-depth trees (pmx_merkle_fixed*, pmx_merkle_frontier_append) ----------------------------------------------------------------
@@ -1673,33 +1639,24 @@ __global__ void __launch_bounds__(256) node_place_kernel(uint4 *elems, const uin
     elems[list[2 * i] * 2 + (gid & 1)] = elems[list[2 * i + 1] * 2 + (gid & 1)];
 }
 hipError_t launch_node_place(uint64_t *elems, const uint64_t *list, size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(node_place_kernel, dim3((unsigned)((k * 2 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<uint4 *>(elems), list, k);
-    return hipGetLastError();
+    return plain(node_place_kernel, k * 2, st, u4(elems), list, k);
 }
 
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,
                              uint64_t *pairs, size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(path_pairs_kernel, dim3((unsigned)((k * 4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),
-                       reinterpret_cast<const uint4 *>(paths), indices, depth, level, reinterpret_cast<uint4 *>(pairs), k);
-    return hipGetLastError();
+    return plain(path_pairs_kernel, k * 4, st, u4(cur), u4(paths), indices, depth, level, u4(pairs), k);
 }
 hipError_t launch_path_children(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level, uint64_t pow,
                                 uint32_t arity, uint64_t *rows, size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(path_children_kernel, dim3((unsigned)((k * 2 * arity + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),
-                       reinterpret_cast<const uint4 *>(paths), indices, depth, level, pow, arity, reinterpret_cast<uint4 *>(rows), k);
-    return hipGetLastError();
+    return plain(path_children_kernel, k * 2 * arity, st, u4(cur), u4(paths), indices, depth, level, pow, arity, u4(rows), k);
 }
 hipError_t launch_paths_gather(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *indices, uint64_t *paths,
                                size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(paths_gather_kernel, dim3((unsigned)((k * depth * 2 * (arity - 1) + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4 *>(nodes), (uint64_t)n_leaves, arity, depth, indices, reinterpret_cast<uint4 *>(paths), k);
-    return hipGetLastError();
+    return plain(paths_gather_kernel, k * depth * 2 * (arity - 1), st, u4(nodes), n_leaves, arity, depth, indices, u4(paths), k);
 }
 hipError_t launch_path_check(const uint64_t *cur, const uint64_t *root, const uint64_t *indices, uint64_t limit, uint8_t *ok,
                              size_t k, hipStream_t st) {
-    hipLaunchKernelGGL(path_check_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const uint4 *>(cur),
-                       reinterpret_cast<const uint4 *>(root), indices, limit, ok, k);
-    return hipGetLastError();
+    return plain(path_check_kernel, k, st, u4(cur), u4(root), indices, limit, ok, k);
 }
 #endif  // PMX_TU
 

@@ -65,7 +65,8 @@ hipError_t launch_squeeze_cut(const DevConfig &c, uint32_t t, uint64_t *states, 
 // member has the signature of its launch_* above whatever the engine - one that runs absorb / squeeze as per-lane kernels does not touch
 // the PassScratch, one that runs them as passes takes its lists from it.  Both the launchers and describe_launch go through the table
 // select_engine returns, so what pmx_ctx_engine_info reports is what a launch runs.
-// Adding an operation: a member here, its line in engine_ops, a launch_* one-liner.
+// Adding an operation: its kernel, a member here, a one-line Launch<Engine> method that hands the kernel and its arguments to
+// Launch<Engine>::enqueue (the one launch body: LDS attribute, geometry, error), its line in engine_ops, a launch_* one-liner.
 struct EngineOps {
     hipError_t (*permute)(const DevConfig &c, uint32_t t, uint64_t *states, size_t n, hipStream_t st);
     hipError_t (*hash)(const DevConfig &c, uint32_t t, const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, size_t n,
