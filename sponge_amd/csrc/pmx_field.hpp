@@ -248,7 +248,7 @@ PMX_FN Fe mont_mul(const Fe &a, const Fe &b, const FieldRt &f) { return mont_dot
 // reduction), so the sum comes out with normalised limbs and no separate addition / magnitude-cap pass.
 // a lazy, b norm, s norm with value < 2^261 - 2p.  Result norm, B < Ba * Bb * p / 2^261 + Bs + 1: the accumulator
 // this is used for (the last step of the quad engine's folded rounds, pmx_permute.hpp: coop_fold_c) grows by about
-// one p per round; the number of rounds is bounded by the host (pmx_prepare.hpp: opt_schedule_lane_headroom).
+// one p per round; the number of rounds is bounded by the host (pmx_derive.hpp: opt_schedule_lane_headroom).
 PMX_FN Fe mont_mul_add(const Fe &a, const Fe &b, const Fe &s, const FieldRt &f) {
     uint32_t m[kN];
     Fe out;
@@ -540,7 +540,7 @@ PMX_FN Fe cols_redc(Cols &t, const FieldRt &f, const Fe *s = nullptr) {
 // x^alpha on the internal form.  5 and 17 use the shortest chains; anything else is MSB-first
 // square-and-multiply seeded with x (alpha is wave-uniform, so the branches are scalar).
 // x may be lazy with B <= 4, or norm with B < 7.6 (a window S-box input with a small-integer history term, pmx_permute.hpp: B^2 < 2^261 / p);
-// the result is norm with B < 1.3 (alpha >= 4; pmx_prepare.hpp: opt_schedule_lane_headroom has the smaller exponents).  `one` = 2^261 mod p.
+// the result is norm with B < 1.3 (alpha >= 4; pmx_derive.hpp: opt_schedule_lane_headroom has the smaller exponents).  `one` = 2^261 mod p.
 // P1: the modulus is 1 mod 2^29 and the products take the complemented digits (mont_sqr_p1 / mont_mul_p1 above): same values mod p, same bounds.
 template <int ALPHA, bool P1 = false>
 PMX_FN Fe fe_sbox(const Fe &x, uint64_t alpha, const Fe &one, const FieldRt &f) {
@@ -641,7 +641,7 @@ PMX_FN Abi fe_to_abi(const Fe &x, const FieldRt &f) {
 }
 
 // ---- ABI <-> internal without a multiplication (optimised schedule) ---------------------------------------------------------
-// The optimised schedule carries its state scaled lane by lane anyway (pmx_prepare.hpp: derive_opt_tables); with the scaling
+// The optimised schedule carries its state scaled lane by lane anyway (pmx_derive.hpp: derive_opt_tables); with the scaling
 // 2^-5 at both ends of the permutation the internal form of a state element x is (x / 32) * 2^261 = x * 2^256 - the ABI
 // residue itself.  Entering is bit-slicing 8 x 32 -> 9 x 29, leaving is the exact reduction to [0, p) and slicing back; the
 // elements a sponge absorbs (added to the state in the same scaled coordinates) and squeezes are converted the same way.

@@ -125,17 +125,119 @@ struct HostField {
         return mul(x, one);
     }
 
+    // x^e in the Montgomery domain, e = the low `bits` bits of the words at `e`
+    U256 pow(const U256 &x, const uint64_t *e, int bits) const {
+        U256 acc = r;
+        for (int bit = bits - 1; bit >= 0; --bit) {
+            acc = mul(acc, acc);
+            if ((e[bit / 64] >> (bit % 64)) & 1) acc = mul(acc, x);
+        }
+        return acc;
+    }
+    U256 pow(const U256 &x, const U256 &e) const { return pow(x, e.l, 256); }
+    U256 pow(const U256 &x, uint64_t e) const { return pow(x, &e, 64); }
+
     // a^(p-2) in the Montgomery domain (Fermat inverse; a != 0)
     U256 inverse(const U256 &a) const {
         U256 e = p, two = {{2, 0, 0, 0}};
         u256_sub(e, e, two);
-        U256 acc = r;
-        for (int bit = 255; bit >= 0; --bit) {
-            acc = mul(acc, acc);
-            if ((e.l[bit / 64] >> (bit % 64)) & 1) acc = mul(acc, a);
-        }
-        return acc;
+        return pow(a, e);
     }
 };
+
+// ---- number theory over a HostField (values in the Montgomery domain) --------------------------------------------------
+inline uint64_t u256_divmod_small(U256 &q, const U256 &a, uint64_t d) {   // q = a / d, returns a % d
+    u128 rem = 0;
+    for (int i = 3; i >= 0; --i) {
+        const u128 cur = (rem << 64) | a.l[i];
+        q.l[i] = (uint64_t)(cur / d);
+        rem = cur % d;
+    }
+    return (uint64_t)rem;
+}
+inline U256 u256_shr(const U256 &a, unsigned k) {   // k < 64
+    U256 r;
+    for (int i = 0; i < 4; ++i) r.l[i] = k ? ((a.l[i] >> k) | (i + 1 < 4 ? a.l[i + 1] << (64 - k) : 0)) : a.l[i];
+    return r;
+}
+inline bool u256_eq(const U256 &a, const U256 &b) { return a.l[0] == b.l[0] && a.l[1] == b.l[1] && a.l[2] == b.l[2] && a.l[3] == b.l[3]; }
+// square root in the Montgomery domain (Tonelli-Shanks); false: a is not a square
+inline bool host_sqrt(const HostField &f, const U256 &a, U256 &root) {
+    if (u256_is_zero(a)) { root = a; return true; }
+    U256 pm1 = f.p;
+    pm1.l[0] -= 1;                                   // p odd: no borrow
+    unsigned S = 0;
+    U256 q = pm1;
+    while (!(q.l[0] & 1)) {
+        q = u256_shr(q, 1);
+        ++S;
+    }
+    const U256 half = u256_shr(pm1, 1), minus_one = f.neg(f.r);
+    if (!u256_eq(f.pow(a, half), f.r)) return false;
+    U256 z = f.r;                                    // a non-residue: 2, 3, 4 ... in the Montgomery domain
+    for (int tries = 0; tries < 200; ++tries) {
+        z = f.add(z, f.r);
+        if (u256_eq(f.pow(z, half), minus_one)) break;
+        if (tries == 199) return false;
+    }
+    U256 qp1 = q;                                    // (q + 1) / 2
+    qp1.l[0] += 1;                                   // q odd: q + 1 even; no carry unless q = 2^64k - 1 (not for a 225 .. 255-bit p - 1 with S >= 1)
+    qp1 = u256_shr(qp1, 1);
+    U256 c = f.pow(z, q), r = f.pow(a, qp1), tt = f.pow(a, q);
+    unsigned m = S;
+    while (!u256_eq(tt, f.r)) {
+        unsigned i = 0;
+        U256 t2 = tt;
+        while (!u256_eq(t2, f.r)) {
+            t2 = f.mul(t2, t2);
+            if (++i == m) return false;
+        }
+        U256 b = c;
+        for (unsigned k = 0; k + i + 1 < m; ++k) b = f.mul(b, b);
+        r = f.mul(r, b);
+        c = f.mul(b, b);
+        tt = f.mul(tt, c);
+        m = i;
+    }
+    root = r;
+    return true;
+}
+// x^(1/e) for a 64-bit e prime to p - 1 (the map is a bijection): x^d with d = e^-1 mod (p - 1) = (1 + k (p - 1)) / e
+inline bool host_root_coprime(const HostField &f, const U256 &x, uint64_t e, U256 &root) {
+    if (e == 1) { root = x; return true; }
+    U256 pm1 = f.p, Q;
+    pm1.l[0] -= 1;
+    const uint64_t R = u256_divmod_small(Q, pm1, e);
+    // k = -R^-1 mod e (extended Euclid on 64-bit values; no inverse: e shares a factor with p - 1)
+    __int128 r0 = (__int128)e, r1 = (__int128)R, t0 = 0, t1 = 1;
+    while (r1 != 0) {
+        const __int128 q = r0 / r1, r2 = r0 - q * r1, t2 = t0 - q * t1;
+        r0 = r1; r1 = r2; t0 = t1; t1 = t2;
+    }
+    if (r0 != 1) return false;
+    __int128 inv = t0 % (__int128)e;
+    if (inv < 0) inv += (__int128)e;
+    const uint64_t k = (uint64_t)(((__int128)e - inv) % (__int128)e);      // k R = -1 (mod e)
+    U256 d = {{0, 0, 0, 0}};                                               // d = k Q + (1 + k R) / e   (k Q < p - 1: no overflow)
+    u128 carry = 0;
+    for (int i = 0; i < 4; ++i) {
+        const u128 v = (u128)Q.l[i] * k + carry;
+        d.l[i] = (uint64_t)v;
+        carry = v >> 64;
+    }
+    const u128 rest = ((u128)k * R + 1) / e;
+    const U256 add = {{(uint64_t)rest, (uint64_t)(rest >> 64), 0, 0}};
+    u256_add(d, d, add);
+    root = f.pow(x, d);
+    return true;
+}
+// is x a 2^a-th power?  (the 2-part of p - 1 is 2^S: x^((p - 1) / 2^min(a, S)) = 1)
+inline bool host_is_2power_residue(const HostField &f, const U256 &x, unsigned a) {
+    if (a == 0 || u256_is_zero(x)) return true;
+    U256 e = f.p;
+    e.l[0] -= 1;
+    for (unsigned i = 0; i < a && !(e.l[0] & 1); ++i) e = u256_shr(e, 1);
+    return u256_eq(f.pow(x, e), f.r);
+}
 
 }  // namespace pmx

@@ -52,7 +52,7 @@ PMX_FN constexpr int mfma_layer_words(int t) { return t * mfma_row_words(t) + t 
 PMX_FN constexpr int mfma_layer_words_io(int n_in, int n_out) { return n_out * mfma_row_words(n_in) + n_out * 16; }
 
 // Windows of partial rounds (round 4).  A partial round applies its S-box to lane 0 only, so over K of them everything but the K
-// S-box outputs is LINEAR: with the carried lanes u in a basis chosen by the host (pmx_prepare.hpp: derive_window_layers) the
+// S-box outputs is LINEAR: with the carried lanes u in a basis chosen by the host (pmx_derive.hpp: derive_window_layers) the
 // S-box inputs are   x_1 (carried),  x_{k+1} = z_k + u_k + sum_{i<k} h_{k,i} z_i   - additions and (K-1)(K-2)/2 products by
 // constants - and the whole linear part of the K rounds (2t-1 products by constants each on the VALU) is ONE layer on the
 // matrix cores: inputs (u_1 .. u_{t-1}, z_1 .. z_K), outputs (x_1, u_1 .. u_{t-1}) of the next window, or the state the full
@@ -91,7 +91,7 @@ static_assert(mfma_row_pairs(PMX_MFMA_MAX_T) && mfma_row_pairs(PMX_MFMA_MAX_T - 
 #endif
 PMX_FN constexpr bool mfma_hist_tab(int t) { return t <= PMX_MFMA_HIST_TAB_MAX_T; }
 // first word of a window's history table when its single constant is a small integer (second word) and there is no table: the host
-// picks the window's free scale for that where it can (pmx_prepare.hpp: derive_window_layers; a table's first word is a 29-bit limb)
+// picks the window's free scale for that where it can (pmx_derive.hpp: derive_window_layers; a table's first word is a 29-bit limb)
 constexpr uint32_t kMfmaHistSmallMarker = 0xffffffffu;
 // ROWS ON THE MATRIX CORES (round 5): the history term is itself a product by constants of values that are cut into bytes for the window's
 // layer anyway - one row of k inputs (z_1 .. z_{k-1}, u_k), its A operand read straight from global memory a whole S-box ahead (k KiB per

@@ -21,7 +21,7 @@ PMX_FN bool is_full_round(uint32_t r, const Rounds &c) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Optimised schedule: exact algebraic rewrites of the same permutation, all done on the constants by the host (pmx_prepare.hpp:
+// Optimised schedule: exact algebraic rewrites of the same permutation, all done on the constants by the host (pmx_derive.hpp:
 // derive_opt_tables and derive_window_layers have the derivations).
 //  (1) Basis change (Poseidon paper, appendix B): the RP partial rounds only touch state[0] non-linearly, so lanes 1..t-1 are carried in a
 //      rotated basis in which the round constants of those lanes leave the partial section (they re-enter through lane 0 and through the
@@ -112,7 +112,7 @@ PMX_FN void permute_hybrid(Fe (&s)[T], Scratch &sc, const OptTables &tb, const R
                     matrix_rows_mfma_w<NIN, T>(W, s, sc, wt, f, 0u, (uint32_t)T, fe_rows);
                 } else {
                     // t = 3: a window of three S-boxes has ONE history term, h_{2,1} z_1 - a product by a shifted table on the VALU, or no
-                    // product at all: where the host found a scale of the window under which the constant is 1 .. 4 (pmx_prepare.hpp: the
+                    // product at all: where the host found a scale of the window under which the constant is 1 .. 4 (pmx_derive.hpp: the
                     // window's free scale) the term is that many lazy additions, normalised with the rest
                     static_assert(K <= 3, "the table form of the history terms covers the single term of a window of three");
                     Fe in[NIN];

@@ -110,10 +110,7 @@ struct HostScratch {
 // itself as plain integer sums (no matrix cores on the host).
 template <int T>
 static int permute_hybrid_mfma_t(const Prepared &pp, uint64_t *states, size_t n) {
-    OptTables tb;
-    tb.ark = pp.consts.data() + pp.opt_offset;
-    tb.mfma = pp.consts.data() + pp.mfma_offset;
-    tb.win = pp.consts.data() + pp.win_offset;
+    const OptTables tb = pp.opt_tables();
     constexpr int KW = mfma_window_for(T);   // the partial section as windows when the width takes them
     if ((int)pp.mfma_window != KW) return PMX_ERR_UNSUPPORTED;
     for (size_t k = 0; k < n; ++k) {
@@ -146,7 +143,7 @@ extern "C" int hc_permute_hybrid_mfma(const pmx_config *cfg, uint64_t *states, s
         default: return PMX_ERR_UNSUPPORTED;
     }
 }
-// how many windows of a t = 3 config carry their history constant as a small integer (pmx_prepare.hpp: the window's free scale);
+// how many windows of a t = 3 config carry their history constant as a small integer (pmx_derive.hpp: the window's free scale);
 // out[0] = windows with a history term, out[1 .. 4] = those with the constant 1 .. 4
 extern "C" int hc_window_small_history(const pmx_config *cfg, uint32_t out[5]) {
     Prepared pp;
@@ -163,6 +160,34 @@ extern "C" int hc_window_small_history(const pmx_config *cfg, uint32_t out[5]) {
         const uint32_t *hist = pp.consts.data() + pp.win_offset + mfma_layer_words(3) + (size_t)w * kPer + kLayer;
         if (hist[0] == kMfmaHistSmallMarker && hist[1] >= 1 && hist[1] <= 4) out[hist[1]] += 1;
     }
+    return PMX_OK;
+}
+// the 32 bytes a 256-bit value is stored as in an int8 table (pmx_prepare.hpp: stored_bytes); returns 0 plain, 1 stored as Y - p, 2 invariant
+// broken (no residue), -1 no modulus
+extern "C" int hc_stored_bytes(const uint64_t modulus[4], const uint64_t y[4], int8_t out[32]) {
+    HostField hf;
+    if (!hf.init(modulus)) return -1;
+    U256 v;
+    std::memcpy(v.l, y, 32);
+    return (int)stored_bytes(hf, v, out);
+}
+// the layout of a config's table: out[0 .. 6] = mds, opt, coop, mfma, win, io offsets and the table's size, in the order of the layout
+// comment (Prepared); out[7 .. 9] = has_opt, mfma_dense, mfma_window; and what pmx_mfma.hpp / pmx_field.hpp say the sections measure:
+// out[10] = words of the dense layers, out[11] = words of the window section with the constant behind it, out[12] = kIoWords
+extern "C" int hc_layout(const pmx_config *cfg, uint64_t out[13]) {
+    Prepared pp;
+    std::string err;
+    int rc = prepare(cfg, pp, err);
+    if (rc) return rc;
+    const size_t offs[7] = {pp.mds_offset, pp.opt_offset, pp.coop_offset, pp.mfma_offset, pp.win_offset, pp.io_offset, pp.consts.size()};
+    for (int i = 0; i < 7; ++i) out[i] = offs[i];
+    out[7] = pp.has_opt;
+    out[8] = pp.mfma_dense;
+    out[9] = pp.mfma_window;
+    const int t = (int)pp.t, K = (int)pp.mfma_window;
+    out[10] = pp.mfma_dense ? (uint64_t)cfg->full_rounds * (uint64_t)mfma_layer_words(t) : 0;
+    out[11] = K ? mfma_window_words(t, K, (cfg->partial_rounds + (size_t)K - 1) / (size_t)K) + kFeStride : 0;
+    out[12] = kIoWords;
     return PMX_OK;
 }
 // the window size this library was compiled with (tests build one library per size)

@@ -94,10 +94,7 @@ static void store_abi(uint64_t *p, const Abi &a) { std::memcpy(p, a.w, 32); }
 // permute_hybrid as HybridEngineP1<T, alpha> instantiates it (P1 = true), the matrix-core layers as integer sums (pmx_mfma.hpp, host form)
 template <int T>
 static int permute_p1_t(const Prepared &pp, uint64_t *states, size_t n) {
-    OptTables tb;
-    tb.ark = pp.consts.data() + pp.opt_offset;
-    tb.mfma = pp.consts.data() + pp.mfma_offset;
-    tb.win = pp.consts.data() + pp.win_offset;
+    const OptTables tb = pp.opt_tables();
     constexpr int KW = mfma_window_for(T);
     if ((int)pp.mfma_window != KW) return PMX_ERR_UNSUPPORTED;
     for (size_t k = 0; k < n; ++k) {

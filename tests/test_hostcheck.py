@@ -190,7 +190,7 @@ def test_permutation_templates_match_c_oracle_on_random_batch(hc):
 def test_identity_lane_magnitudes_stay_inside_their_bounds(hc):
     """The identity lanes of the quad engine's sparse partial rounds (t = 3) are updated without a magnitude cap (mont_mul_add): they grow
     by at most 1.0204 p per round and must stay below 2^261 (normalised limbs).  The host build reports every lane and every row-0
-    output of the partial section: limbs < 2^29, lanes inside the worst-case line pmx_prepare.hpp budgets for (opt_schedule_lane_headroom),
+    output of the partial section: limbs < 2^29, lanes inside the worst-case line pmx_derive.hpp budgets for (opt_schedule_lane_headroom),
     row 0 small."""
     from sponge_amd import synth
     import sponge_amd as S
@@ -402,7 +402,7 @@ def test_a_zero_capacity_lane_skips_its_first_sbox(hc, t, alpha):
                                                      (O.BLS12_381_FR, 255, 8, 57, 5, [19, 0, 0, 0, 0]), (O.BLS12_381_FR, 255, 8, 31, 17, [10, 0, 0, 0, 0]),
                                                      (O.BN254_FR, 254, 8, 31, 17, [10, 10, 0, 0, 0]), (O.BLS12_381_FR, 255, 8, 13, 257, [4, 0, 0, 0, 0])])
 def test_a_windows_free_scale_turns_its_history_constant_into_a_small_integer(hc, p, bits, rf, rp, alpha, want):
-    """pmx_prepare.hpp (derive_window_layers): x^_1 of a window may be carried scaled by any lambda; the one history constant of a t = 3
+    """pmx_derive.hpp (derive_window_layers): x^_1 of a window may be carried scaled by any lambda; the one history constant of a t = 3
     window becomes h lambda^(alpha^2 - alpha), and where s / h has such a root for s in 1 .. 4 the kernel adds z^_1 s times instead of
     multiplying by a table (pmx_permute.hpp).  The constant depends on the MDS matrix and the exponent only, so a config's windows all
     get the same s or none: BASELINE's C2 config gets 1, BN254 t = 3 (8, 57) gets 2, BN254 with alpha = 17 gets 1; BLS (8, 57), the
@@ -430,7 +430,7 @@ def test_a_windows_free_scale_turns_its_history_constant_into_a_small_integer(hc
 
 @pytest.mark.parametrize("K", [9, 1, 4, 6])
 def test_partial_rounds_as_windows_every_size_and_width(K):
-    """pmx_mfma.hpp / pmx_prepare.hpp (derive_window_layers): the matrix-core engines of t = 3..9 run their partial rounds as windows
+    """pmx_mfma.hpp / pmx_derive.hpp (derive_window_layers): the matrix-core engines of t = 3..9 run their partial rounds as windows
     of K S-boxes closed by ONE layer each - an exact rewrite derived on the host (basis of the carried lanes chosen so that later
     S-box inputs are sums of an earlier output, a carried coordinate and K - 2 products at most; the first window takes RP mod K).
     Host build of the same templates and tables against the big-integer oracle: the shipped size 9 = the width at most (57 = 3 + 6 x 9
