@@ -45,9 +45,10 @@ int hip_fail(hipError_t e, const char *what) {
 
 using namespace pmx;
 
-namespace pmx {
-
-int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
+// ---- the call scope (pmx_ctx.hpp) ---------------------------------------------------------------------
+// Grow-only device staging: at least `bytes` bytes of ctx->scratch[slot].  Growing FREES the old block, which is why HostCall::stage
+// hands a slot out once per call.
+static int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
     if (bytes == 0) bytes = 16;
     if (ctx->scratch_bytes[slot] < bytes) {
         void *old = ctx->scratch[slot];
@@ -61,15 +62,43 @@ int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out) {
     return PMX_OK;
 }
 
-}  // namespace pmx
+int HostCall::stage(const Staging &layout, char **base) {
+    *base = nullptr;
+    if (layout.overflowed()) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    if (slots_ == 4) return set_error(PMX_ERR_HOST, "a host-buffer call asked for a fifth staging block");
+    void *d = nullptr;
+    if (int rc = ctx_scratch(ctx, slots_, layout.bytes(), &d)) return rc;
+    ++slots_;
+    *base = (char *)d;
+    return PMX_OK;
+}
 
-// The context's page-locked block, allocated on first use: what a host-buffer call of at most kSmallCallBytes stages through, one copy
-// each way (the caller holds host_lock).
-static constexpr size_t kSmallCallBytes = 64 * 1024;
-static int ctx_pinned(pmx_ctx *ctx, char **out) {
+int HostCall::pinned_block(char **out) {
     if (!ctx->pinned) PMX_HIP(hipHostMalloc(&ctx->pinned, kSmallCallBytes, hipHostMallocDefault));
     *out = (char *)ctx->pinned;
     return PMX_OK;
+}
+
+static bool is_pinned(const void *p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();   // an ordinary (unregistered) host pointer: clear the sticky error
+        return false;
+    }
+    return attr.type == hipMemoryTypeHost;
+}
+
+bool HostCall::pin(const void *p, size_t bytes, bool answer_wanted) {
+    if (!p || bytes == 0) return true;
+    if (!answer_wanted && bytes < ScopedPin::kMinBytes) return false;
+    if (is_pinned(p)) return true;
+    if (bytes < ScopedPin::kMinBytes || pinned_ == 2) return false;
+    if (hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    pins_[pinned_++].ptr = const_cast<void *>(p);
+    return true;
 }
 
 // The host-buffer pipeline of a batch whose buffers are page-locked: chunk i is uploaded on `stream`, computed on `stream2` behind the
@@ -450,35 +479,6 @@ extern "C" int pmx_stream_synchronize(int device, void *stream) {
     return PMX_OK;
 }
 
-static bool is_pinned(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();   // an ordinary (unregistered) host pointer: clear the sticky error
-        return false;
-    }
-    return attr.type == hipMemoryTypeHost;
-}
-
-// A pageable buffer of a large call is page-locked for the length of the call (hipHostRegister: 4.2 ms for the 96 MiB of 2^20 t = 3
-// states, unregister 0.1 ms - profiles/r06/g_host_path_probe.txt) so that it takes the same pipeline: 7 ms instead of the 8 ... 20 ms of the
-// runtime's own staging through bounce buffers.  A registration that fails (locked-memory limit, a range that is not plain memory) leaves
-// the buffer as it is and the call takes the single-chunk path.
-struct ScopedPin {
-    void *ptr = nullptr;
-    ScopedPin(const void *p, size_t bytes) {
-        if (p && bytes >= kMinBytes && !is_pinned(p)) {
-            if (hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) == hipSuccess) ptr = const_cast<void *>(p);
-            else (void)hipGetLastError();
-        }
-    }
-    ~ScopedPin() {
-        if (ptr && hipHostUnregister(ptr) != hipSuccess) (void)hipGetLastError();
-    }
-    ScopedPin(const ScopedPin &) = delete;
-    ScopedPin &operator=(const ScopedPin &) = delete;
-    static constexpr size_t kMinBytes = (size_t)16 << 20;   // below this the registration costs more than it saves
-};
-
 // chunks of a batch for the pinned pipeline: rows per chunk (a multiple of 256).  A chunk is a kernel launch of its own: at least 65536
 // rows (below that a launch is bound by one permutation's latency, at t = 3 on the lone-permutation kernels), at most kPipeChunks chunks
 // (2^20 t = 3 states: 16 chunks 2.50 ms, 8 chunks 2.56, 32 chunks 4.2 - profiles/r06/g_host_path_probe_graded_chunks_and_zero_copy_not_kept.txt)
@@ -504,17 +504,16 @@ extern "C" int pmx_permute_batch(pmx_ctx *ctx, uint64_t *states, size_t n) {
     PMX_ABI_BEGIN("pmx_permute_batch")
     if (!ctx || (!states && n)) return set_error(PMX_ERR_ARG, "pmx_permute_batch: null pointer");
     if (n == 0) return PMX_OK;
-    PMX_BIND(ctx);
+    PMX_HOST_CALL(call, ctx);
     int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
     const size_t row = (size_t)ctx->t * 32;
     size_t bytes = 0;
     if ((rc = batch_bytes(n, ctx->t, &bytes))) return rc;
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, bytes, &d))) return rc;
-    ScopedPin pin(states, bytes);   // (declared in front of the drain: unregistered only after the drain has found the streams idle)
-    StreamDrain drain{ctx};
-    const size_t step = is_pinned(states) ? pipeline_rows(n) : n;   // pinned: upload / kernel / download overlap, both directions at once
+    Staging layout;
+    layout.add(n, row);   // the states [n][t][4]
+    char *d = nullptr;
+    if ((rc = call.stage(layout, &d))) return rc;
+    const size_t step = call.pin(states, bytes) ? pipeline_rows(n) : n;   // pinned: upload / kernel / download overlap, both directions at once
     return host_pipeline(
         ctx, n, step,
         [&](size_t first, size_t cnt, hipStream_t st) -> int {
@@ -550,18 +549,18 @@ extern "C" int pmx_hash_batch(pmx_ctx *ctx, const uint64_t *in, size_t in_len, u
     PMX_ABI_BEGIN("pmx_hash_batch")
     if (!ctx || (!in && n && in_len) || (!out && n && out_len)) return set_error(PMX_ERR_ARG, "pmx_hash_batch: null pointer");
     if (n == 0) return PMX_OK;
-    PMX_BIND(ctx);
+    PMX_HOST_CALL(call, ctx);
     int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
     size_t in_bytes = 0, out_bytes = 0;
     if ((rc = batch_bytes(n, in_len, &in_bytes)) || (rc = batch_bytes(n, out_len, &out_bytes))) return rc;
-    void *d_in = nullptr, *d_out = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, in_bytes, &d_in))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, out_bytes, &d_out))) return rc;
-    ScopedPin pin_in(in, in_bytes), pin_out(out, out_bytes);   // (in front of the drain: see pmx_permute_batch)
-    StreamDrain drain{ctx};
     const size_t in_row = in_len * 32, out_row = out_len * 32;
-    const size_t step = ((!in_bytes || is_pinned(in)) && (!out_bytes || is_pinned(out))) ? pipeline_rows(n) : n;
+    Staging rows_in, rows_out;
+    rows_in.add(n, in_row);     // the inputs [n][in_len][4]
+    rows_out.add(n, out_row);   // the digests [n][out_len][4]
+    char *d_in = nullptr, *d_out = nullptr;
+    if ((rc = call.stage(rows_in, &d_in)) || (rc = call.stage(rows_out, &d_out))) return rc;
+    const bool in_pinned = call.pin(in, in_bytes), out_pinned = call.pin(out, out_bytes, in_pinned);   // (a large `out` is registered either way)
+    const size_t step = in_pinned && out_pinned ? pipeline_rows(n) : n;
     return host_pipeline(
         ctx, n, step,
         [&](size_t first, size_t cnt, hipStream_t st) -> int {
@@ -684,38 +683,40 @@ static int check_modes(const pmx_ctx *ctx, const uint32_t *tag, const uint32_t *
     return PMX_OK;
 }
 
-// n sponges resident on the device for the length of a host-buffer call: [states | tag | index] in staging slot 0, the mode words on
-// 16-byte boundaries.  The caller holds host_lock, drains the streams, and reads nothing back before its last piece is enqueued: a call
-// that fails half way leaves the caller's sponges as they were.
+// n sponges resident on the device for the length of a host-buffer call: [states | io | tag | index] in one staging block, where `io`
+// is the data of a packed call (sponge_host) and empty otherwise.  The caller reads nothing back before its last piece is enqueued: a
+// call that fails half way leaves the caller's sponges as they were.  (st_bytes: the caller's batch_bytes(n, t).)
 struct ResidentSponges {
-    uint64_t *states = nullptr;
-    uint32_t *tag = nullptr, *index = nullptr;
-    size_t n = 0, st_bytes = 0, bytes = 0;
+    Staging layout;
+    size_t n, st_bytes, o_io, o_tag, o_index;
+    char *d = nullptr;
 
-    int place(pmx_ctx *ctx, size_t n_, size_t st_bytes_) {
-        const size_t words = (n_ * 4 + 15) / 16 * 16;
-        void *d = nullptr;
-        if (int rc = ctx_scratch(ctx, 0, st_bytes_ + 2 * words, &d)) return rc;
-        n = n_, st_bytes = st_bytes_, bytes = st_bytes_ + 2 * words;
-        states = (uint64_t *)d;
-        tag = (uint32_t *)((char *)d + st_bytes);
-        index = (uint32_t *)((char *)d + st_bytes + words);
-        return PMX_OK;
+    ResidentSponges(size_t n_, size_t st_bytes_, size_t io_bytes) : n(n_), st_bytes(st_bytes_) {
+        layout.add(st_bytes, 1);
+        o_io = layout.add(io_bytes, 1);
+        o_tag = layout.add(n, 4);
+        o_index = layout.add(n, 4);
+        layout.add(0, 1);   // the block ends on a boundary: the packed call copies bytes() each way, the size it has always copied
     }
+    int place(HostCall &call) { return call.stage(layout, &d); }
+    uint64_t *states() const { return (uint64_t *)d; }
+    uint64_t *io() const { return (uint64_t *)(d + o_io); }
+    uint32_t *tag() const { return (uint32_t *)(d + o_tag); }
+    uint32_t *index() const { return (uint32_t *)(d + o_index); }
     int upload(const uint64_t *h_states, const uint32_t *h_tag, const uint32_t *h_index, hipStream_t st) const {
-        PMX_HIP(hipMemcpyAsync(states, h_states, st_bytes, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(tag, h_tag, n * 4, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(index, h_index, n * 4, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(states(), h_states, st_bytes, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(tag(), h_tag, n * 4, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(index(), h_index, n * 4, hipMemcpyHostToDevice, st));
         return PMX_OK;
     }
     int fresh(hipStream_t st) const {   // zero state, Absorbing{0} (mod.rs:219-230)
-        PMX_HIP(hipMemsetAsync(states, 0, bytes, st));
+        PMX_HIP(hipMemsetAsync(d, 0, layout.bytes(), st));
         return PMX_OK;
     }
     int download(uint64_t *h_states, uint32_t *h_tag, uint32_t *h_index, hipStream_t st) const {
-        PMX_HIP(hipMemcpyAsync(h_states, states, st_bytes, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(h_tag, tag, n * 4, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(h_index, index, n * 4, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(h_states, states(), st_bytes, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(h_tag, tag(), n * 4, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(h_index, index(), n * 4, hipMemcpyDeviceToHost, st));
         return PMX_OK;
     }
 };
@@ -730,11 +731,39 @@ static int copy_columns(void *dst, size_t dst_pitch, const void *src, size_t src
     return PMX_OK;
 }
 
+// The resident walk of the host absorb and squeeze entries, in native elements: the sponges up once; every piece of fixed_piece
+// (pmx_host_pieces.hpp; a call within kMaxPasses rates is its one piece) through `step`, a _dev entry on ctx->stream, with its columns
+// moved up in front of it (`up`) or down behind it (`down`) between the caller's rows - `row` bytes each, of which a native element
+// yields `unit`, the last one what is left - and a packed [n][width] block; the sponges down once.  An error half way through a call
+// of several pieces leaves the caller's states and mode words untouched (a squeeze's `out` holds the pieces that were done).
+template <class Step>
+static int resident_walk(HostCall &call, uint64_t *states, uint32_t *tag, uint32_t *index, size_t n, size_t st_bytes, size_t elems, size_t unit,
+                         size_t row, const char *up, char *down, Step &&step) {
+    const size_t rate = call.ctx->dev.rounds.rate, max_elems = kMaxPasses * rate;
+    ResidentSponges sp(n, st_bytes, 0);
+    Staging columns;
+    columns.add(n, std::min(row, max_elems * unit));   // the widest piece's columns
+    char *d_io = nullptr;
+    int rc = PMX_OK;
+    if ((rc = sp.place(call)) || (rc = call.stage(columns, &d_io))) return rc;
+    hipStream_t st = call.ctx->stream;
+    if ((rc = sp.upload(states, tag, index, st))) return rc;
+    size_t done = 0;   // elements per sponge so far
+    do {
+        const size_t piece = fixed_piece(done, elems, max_elems, rate);
+        const size_t col = done * unit, width = std::min(row - col, piece * unit);
+        if (up && (rc = copy_columns(d_io, width, up + col, row, width, n, hipMemcpyHostToDevice, st))) return rc;
+        if ((rc = step(sp, d_io, piece, width, st))) return rc;
+        if (down && (rc = copy_columns(down + col, row, d_io, width, width, n, hipMemcpyDeviceToHost, st))) return rc;
+        done += piece;
+    } while (done < elems);
+    if ((rc = sp.download(states, tag, index, st))) return rc;
+    PMX_HIP(hipStreamSynchronize(st));
+    return PMX_OK;
+}
+
 // The host absorb and squeeze of field elements take any length, as the reference does (mod.rs:232-254, 321-341): a small call goes
-// through the context's page-locked block, every other call is the resident walk - the sponges up once, every piece of fixed_piece
-// (pmx_host_pieces.hpp; a call within kMaxPasses rates is its one piece) through the _dev entry on ctx->stream with its columns moved
-// up in front of it (absorb) or down behind it (squeeze), the sponges down once.  An error half way through a call of several pieces
-// leaves the caller's states and mode words untouched (a squeeze's `out` holds the pieces that were done).
+// through the context's page-locked block, every other call is the resident walk.
 static int sponge_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *index, const uint64_t *in, uint64_t *out,
                        size_t len, size_t n, bool absorb) {
     PMX_ABI_BEGIN("pmx_sponge_*_batch")
@@ -745,62 +774,37 @@ static int sponge_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
     int rc = check_modes(ctx, tag, index, n);
     if (rc) return rc;
     const size_t rate = ctx->dev.rounds.rate, max_len = kMaxPasses * rate;
-    PMX_BIND(ctx);
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
+    PMX_HOST_CALL(call, ctx);
     size_t st_bytes = 0, io_bytes = 0;   // (io: the widest piece)
     if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(n, std::min(len, max_len), &io_bytes))) return rc;
+    auto step = [&](const ResidentSponges &sp, char *d_io, size_t piece, size_t, hipStream_t st) -> int {
+        if (absorb) return pmx_sponge_absorb_batch_dev(ctx, sp.states(), sp.tag(), sp.index(), (const uint64_t *)d_io, piece, n, st);
+        return pmx_sponge_squeeze_batch_dev(ctx, sp.states(), sp.tag(), sp.index(), (uint64_t *)d_io, piece, n, st);
+    };
     // A handful of sponges (the single PoseidonSponge of the trait shims is n = 1): the call is all latency, and eight
     // separate copies from pageable memory cost as much as the permutation itself.  Pack [states | io | tag | index] into
     // the context's page-locked block: one copy in, the kernel, one copy out.  (One sponge's max_len elements are 2 MiB and more:
     // a call of several pieces never fits.)
-    const size_t words = (n * 4 + 15) / 16 * 16, packed = st_bytes + io_bytes + 2 * words;
-    if (packed <= kSmallCallBytes) {
+    ResidentSponges sp(n, st_bytes, io_bytes);
+    const size_t packed = sp.layout.bytes();
+    if (!sp.layout.overflowed() && packed <= kSmallCallBytes) {
         char *h = nullptr;
-        if ((rc = ctx_pinned(ctx, &h))) return rc;
-        void *d = nullptr;
-        if ((rc = ctx_scratch(ctx, 0, packed, &d))) return rc;
-        char *dd = (char *)d;
-        const size_t o_io = st_bytes, o_tag = st_bytes + io_bytes, o_idx = o_tag + words;
+        if ((rc = call.pinned_block(&h)) || (rc = sp.place(call))) return rc;
         std::memcpy(h, states, st_bytes);
-        if (absorb) std::memcpy(h + o_io, in, io_bytes);
-        std::memcpy(h + o_tag, tag, n * 4);
-        std::memcpy(h + o_idx, index, n * 4);
-        StreamDrain drain{ctx};
-        PMX_HIP(hipMemcpyAsync(dd, h, packed, hipMemcpyHostToDevice, ctx->stream));
-        if (absorb) rc = pmx_sponge_absorb_batch_dev(ctx, (uint64_t *)dd, (uint32_t *)(dd + o_tag), (uint32_t *)(dd + o_idx), (const uint64_t *)(dd + o_io), len, n, ctx->stream);
-        else rc = pmx_sponge_squeeze_batch_dev(ctx, (uint64_t *)dd, (uint32_t *)(dd + o_tag), (uint32_t *)(dd + o_idx), (uint64_t *)(dd + o_io), len, n, ctx->stream);
-        if (rc) return rc;
-        PMX_HIP(hipMemcpyAsync(h, dd, packed, hipMemcpyDeviceToHost, ctx->stream));
+        if (absorb) std::memcpy(h + sp.o_io, in, io_bytes);
+        std::memcpy(h + sp.o_tag, tag, n * 4);
+        std::memcpy(h + sp.o_index, index, n * 4);
+        PMX_HIP(hipMemcpyAsync(sp.d, h, packed, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = step(sp, sp.d + sp.o_io, len, 0, ctx->stream))) return rc;
+        PMX_HIP(hipMemcpyAsync(h, sp.d, packed, hipMemcpyDeviceToHost, ctx->stream));
         PMX_HIP(hipStreamSynchronize(ctx->stream));
         std::memcpy(states, h, st_bytes);
-        std::memcpy(tag, h + o_tag, n * 4);
-        std::memcpy(index, h + o_idx, n * 4);
-        if (!absorb && io_bytes) std::memcpy(out, h + o_io, io_bytes);
+        std::memcpy(tag, h + sp.o_tag, n * 4);
+        std::memcpy(index, h + sp.o_index, n * 4);
+        if (!absorb && io_bytes) std::memcpy(out, h + sp.o_io, io_bytes);
         return PMX_OK;
     }
-    ResidentSponges sp;
-    void *d_io = nullptr;   // slot 1: the piece's columns, packed [n][piece]
-    if ((rc = sp.place(ctx, n, st_bytes))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, io_bytes, &d_io))) return rc;
-    StreamDrain drain{ctx};
-    hipStream_t st = ctx->stream;
-    if ((rc = sp.upload(states, tag, index, st))) return rc;
-    size_t done = 0;   // elements per sponge so far
-    do {
-        const size_t piece = fixed_piece(done, len, max_len, rate);
-        if (absorb) {
-            if ((rc = copy_columns(d_io, piece * 32, in + done * 4, len * 32, piece * 32, n, hipMemcpyHostToDevice, st))) return rc;
-            rc = pmx_sponge_absorb_batch_dev(ctx, sp.states, sp.tag, sp.index, (const uint64_t *)d_io, piece, n, st);
-        } else {
-            rc = pmx_sponge_squeeze_batch_dev(ctx, sp.states, sp.tag, sp.index, (uint64_t *)d_io, piece, n, st);
-            if (!rc) rc = copy_columns(out + done * 4, len * 32, d_io, piece * 32, piece * 32, n, hipMemcpyDeviceToHost, st);
-        }
-        if (rc) return rc;
-        done += piece;
-    } while (done < len);
-    if ((rc = sp.download(states, tag, index, st))) return rc;
-    PMX_HIP(hipStreamSynchronize(st));
-    return PMX_OK;
+    return resident_walk(call, states, tag, index, n, st_bytes, len, 32, len * 32, (const char *)in, (char *)out, step);
     PMX_ABI_END
 }
 
@@ -846,43 +850,27 @@ extern "C" int pmx_sponge_squeeze_bits_batch_dev(pmx_ctx *ctx, uint64_t *d_state
     return squeeze_cut_dev(ctx, d_states, d_mode_tag, d_mode_index, d_out, num_bits, n, stream, true, "pmx_sponge_squeeze_bits_batch_dev");
 }
 
-// Host buffers: the resident walk of sponge_host, in native elements - a call beyond kMaxPasses rates of them is cut on element
-// boundaries by fixed_piece (pmx_host_pieces.hpp), the truncation falls into the last piece, and every piece's [n][piece] block comes
-// down into its columns of the caller's rows: n * len bytes over the link in all.
+// Host buffers: the resident walk, in native elements - a call beyond kMaxPasses rates of them is cut on element boundaries, the
+// truncation falls into the last piece, and every piece's [n][width] block comes down into its columns of the caller's rows: n * len
+// bytes over the link in all.
 static int squeeze_cut_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *index, uint8_t *out, size_t len, size_t n, bool bits,
                             const char *who) {
     PMX_ABI_BEGIN(who)
     if (!ctx || ((!states || !tag || !index) && n)) return set_error(PMX_ERR_ARG, "%s: null pointer", who);
     if (n == 0) return PMX_OK;
     if (!out && len) return set_error(PMX_ERR_ARG, "%s: null data pointer", who);
+    // (the caller's `out`, n rows of len bytes, which the column copies index: not a staging size)
     if (len && n > SIZE_MAX / len) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
     int rc = check_modes(ctx, tag, index, n);
     if (rc) return rc;
     const size_t unit = cut_unit(ctx->dev.field, bits), elems = cut_elems(len, (uint32_t)unit);
-    const size_t rate = ctx->dev.rounds.rate, max_elems = kMaxPasses * rate;
     size_t st_bytes = 0, piece_bytes = 0;
-    if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(n, std::min(elems, max_elems), &piece_bytes))) return rc;
-    const size_t widest = std::min(len, max_elems * unit);   // output units of the longest piece
-    PMX_BIND(ctx);
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    ResidentSponges sp;
-    void *d_io = nullptr;
-    if ((rc = sp.place(ctx, n, st_bytes))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, n * widest, &d_io))) return rc;
-    StreamDrain drain{ctx};
-    hipStream_t st = ctx->stream;
-    if ((rc = sp.upload(states, tag, index, st))) return rc;
-    size_t done = 0;   // elements squeezed so far
-    do {
-        const size_t piece = fixed_piece(done, elems, max_elems, rate);
-        const size_t col = done * unit, width = std::min(len - col, piece * unit);
-        if ((rc = squeeze_cut_dev(ctx, sp.states, sp.tag, sp.index, (uint8_t *)d_io, width, n, st, bits, who))) return rc;
-        if ((rc = copy_columns(out + col, len, d_io, width, width, n, hipMemcpyDeviceToHost, st))) return rc;
-        done += piece;
-    } while (done < elems);
-    if ((rc = sp.download(states, tag, index, st))) return rc;
-    PMX_HIP(hipStreamSynchronize(st));
-    return PMX_OK;
+    if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(n, std::min(elems, kMaxPasses * ctx->dev.rounds.rate), &piece_bytes))) return rc;
+    PMX_HOST_CALL(call, ctx);
+    return resident_walk(call, states, tag, index, n, st_bytes, elems, unit, len, nullptr, (char *)out,
+                         [&](const ResidentSponges &sp, char *d_io, size_t, size_t width, hipStream_t st) -> int {
+                             return squeeze_cut_dev(ctx, sp.states(), sp.tag(), sp.index(), (uint8_t *)d_io, width, n, st, bits, who);
+                         });
     PMX_ABI_END
 }
 
@@ -919,21 +907,20 @@ extern "C" int pmx_sponge_grind(pmx_ctx *ctx, const uint64_t *state, uint32_t mo
         *found_out = 1;
         return PMX_OK;
     }
-    PMX_BIND(ctx);
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // staging: [state t x 32 bytes | the smallest accepted nonce | whether there is one], one copy up, 16 bytes down per chunk
+    PMX_HOST_CALL(call, ctx);
+    // one copy up, 16 bytes down per chunk
+    Staging layout;
     const size_t st_bytes = (size_t)ctx->t * 32;
-    char *h = nullptr;
-    if ((rc = ctx_pinned(ctx, &h))) return rc;
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, st_bytes + 16, &d))) return rc;
-    uint64_t *h_res = (uint64_t *)(h + st_bytes), *d_state = (uint64_t *)d, *d_res = (uint64_t *)((char *)d + st_bytes);
+    layout.add(ctx->t, 32);                       // the state
+    const size_t o_res = layout.add(2, 8);        // the smallest accepted nonce | whether there is one
+    char *h = nullptr, *d = nullptr;
+    if ((rc = call.pinned_block(&h)) || (rc = call.stage(layout, &d))) return rc;
+    uint64_t *h_res = (uint64_t *)(h + o_res), *d_state = (uint64_t *)d, *d_res = (uint64_t *)(d + o_res);
     std::memcpy(h, state, st_bytes);
     h_res[0] = UINT64_MAX;
     h_res[1] = 0;
-    StreamDrain drain{ctx};
     hipStream_t st = ctx->stream;
-    PMX_HIP(hipMemcpyAsync(d, h, st_bytes + 16, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(d, h, layout.bytes(), hipMemcpyHostToDevice, st));
     uint32_t index = mode_index;
     if (mode_tag == PMX_MODE_SQUEEZING || index == ctx->dev.rounds.rate) {   // mod.rs:241-244, 250: the same for every nonce
         PMX_HIP(launch_permute(ctx->dev, ctx->t, d_state, 1, st));
@@ -1022,19 +1009,18 @@ static int varlen_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
     if ((rc = batch_bytes(n, ctx->t, &st_bytes)) || (rc = batch_bytes(total, 1, &in_bytes)) || (rc = batch_bytes(n, hash ? out_len : 0, &out_bytes)))
         return rc;
     if (hash && (rc = check_pass_count(ctx, PMX_OP_SQUEEZE, n, out_len, who))) return rc;
-    PMX_BIND(ctx);
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: the n resident sponges; slot 1: the input (or one piece of it); slot 2: the offsets; slot 3: the digests
-    ResidentSponges sp;
-    void *d_in = nullptr, *d_off = nullptr, *d_out = nullptr;
-    if ((rc = sp.place(ctx, n, st_bytes))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, pieces > 1 ? std::min(in_bytes, n * piece * 32) : in_bytes, &d_in))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, (n + 1) * 8, &d_off))) return rc;
-    if (hash && (rc = ctx_scratch(ctx, 3, out_bytes, &d_out))) return rc;
-    StreamDrain drain{ctx};
+    std::vector<uint64_t> off(n + 1), packed;   // (in front of the scope: uploaded from until its drain)
+    PMX_HOST_CALL(call, ctx);
+    ResidentSponges sp(n, st_bytes, 0);
+    Staging input, row_offsets, digests;
+    input.add(pieces > 1 ? std::min(in_bytes, n * piece * 32) : in_bytes, 1);   // the input, or one piece of it
+    row_offsets.add(n + 1, 8);
+    digests.add(out_bytes, 1);
+    char *d_in = nullptr, *d_off = nullptr, *d_out = nullptr;
+    if ((rc = sp.place(call)) || (rc = call.stage(input, &d_in)) || (rc = call.stage(row_offsets, &d_off))) return rc;
+    if (hash && (rc = call.stage(digests, &d_out))) return rc;
     hipStream_t st = ctx->stream;
     if ((rc = hash ? sp.fresh(st) : sp.upload(states, tag, index, st))) return rc;
-    std::vector<uint64_t> off(n + 1), packed;
     for (size_t k = 0; k < pieces; ++k) {
         // piece k of every row (ragged_range), rebased so that the uploaded input starts at offset 0
         const uint64_t *src = in + offsets[0] * 4;
@@ -1049,13 +1035,13 @@ static int varlen_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
         }
         if (off[n]) PMX_HIP(hipMemcpyAsync(d_in, src, off[n] * 32, hipMemcpyHostToDevice, st));
         PMX_HIP(hipMemcpyAsync(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-        if ((rc = pmx_sponge_absorb_varlen_batch_dev(ctx, sp.states, sp.tag, sp.index, (const uint64_t *)d_in, (const uint64_t *)d_off,
+        if ((rc = pmx_sponge_absorb_varlen_batch_dev(ctx, sp.states(), sp.tag(), sp.index(), (const uint64_t *)d_in, (const uint64_t *)d_off,
                                                      std::min(longest, piece), n, st)))
             return rc;
         PMX_HIP(hipStreamSynchronize(st));   // (`off` and `packed` are rewritten for the next piece)
     }
     if (hash) {
-        if ((rc = pmx_sponge_squeeze_batch_dev(ctx, sp.states, sp.tag, sp.index, (uint64_t *)d_out, out_len, n, st))) return rc;
+        if ((rc = pmx_sponge_squeeze_batch_dev(ctx, sp.states(), sp.tag(), sp.index(), (uint64_t *)d_out, out_len, n, st))) return rc;
         PMX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     } else if ((rc = sp.download(states, tag, index, st))) {
         return rc;
@@ -1078,9 +1064,9 @@ extern "C" int pmx_hash_varlen_batch(pmx_ctx *ctx, const uint64_t *in, const uin
 // A trace / LDE matrix to its row digests and the tree over them (include/poseidon_mi355x.h has the contract): leaf_i = (new; absorb(row i);
 // squeeze_native(1))[0] (mod.rs:219-254, 321-341), the hash row of pmx_hash_batch at out_len = 1, read where the matrix lies.  The
 // index arithmetic is pmx_matrix_shape.hpp's.  The matrix goes up in slabs of rows (PMX_MATRIX_SLAB_BYTES of them, 65536 rows at least:
-// profiles/matrix_commit/README.md has the sweep) through two slab buffers (staging slots 1 and 2):
+// profiles/matrix_commit/README.md has the sweep) through two slab buffers (staging blocks of their own):
 // `stream` uploads slab s + 1 while `stream2` hashes slab s (hash_strided_kernel, the slab's own strides) straight into rows [a, b) of
-// the node array (slot 0); an upload into a buffer waits for the hash that read it last.  The tree walk and the one download follow
+// the node array; an upload into a buffer waits for the hash that read it last.  The tree walk and the one download follow
 // on `stream2`.  A column-major slab is ONE 2-D copy into a packed column-major buffer of leading dimension b - a.
 namespace {
 
@@ -1104,15 +1090,17 @@ int matrix_arity_fits(const pmx_ctx *ctx, uint32_t arity) {
     return PMX_OK;
 }
 
-// rows [0, n_rows) of `matrix` (host) hashed into d_leaves [n_rows][4]; everything ends enqueued on ctx->stream2.  The caller holds the
-// host lock, has bound the device and drains the streams.  `src` is page-locked or small (see matrix_host).
-int matrix_leaves_enqueue(pmx_ctx *ctx, const char *src, size_t n_rows, size_t row_len, uint32_t layout, uint64_t *d_leaves) {
+// rows [0, n_rows) of `matrix` (host) hashed into d_leaves [n_rows][4]; everything ends enqueued on ctx->stream2.  `src` is
+// page-locked or small (see matrix_host).
+int matrix_leaves_enqueue(HostCall &call, const char *src, size_t n_rows, size_t row_len, uint32_t layout, uint64_t *d_leaves) {
+    pmx_ctx *ctx = call.ctx;
     int rc = PMX_OK;
     const uint64_t slab_rows = matrix_slab_rows_of(n_rows, row_len), slabs = matrix_slabs(n_rows, slab_rows);
-    const size_t slab_bytes = (size_t)slab_rows * row_len * 32;
-    void *d_slab[2] = {nullptr, nullptr};
-    if ((rc = ctx_scratch(ctx, 1, slab_bytes, &d_slab[0]))) return rc;
-    if (slabs > 1 && (rc = ctx_scratch(ctx, 2, slab_bytes, &d_slab[1]))) return rc;
+    Staging slab_layout;
+    slab_layout.add(slab_layout.times((size_t)slab_rows, row_len), 32);   // one slab of rows; a second block of it when there are several
+    char *d_slab[2] = {nullptr, nullptr};
+    if ((rc = call.stage(slab_layout, &d_slab[0]))) return rc;
+    if (slabs > 1 && (rc = call.stage(slab_layout, &d_slab[1]))) return rc;
     for (uint64_t s = 0; s < slabs; ++s) {
         const MatrixSlab slab = matrix_slab_at(n_rows, slab_rows, s);
         const MatrixCopy cp = matrix_slab_copy(layout, n_rows, row_len, slab);
@@ -1142,25 +1130,27 @@ int matrix_host(pmx_ctx *ctx, const uint64_t *matrix, size_t n_rows, size_t row_
         if (int rc = pmx_merkle_ragged_shape(n_rows, arity, &depth, &n_nodes)) return rc;
         if (int rc = matrix_arity_fits(ctx, arity)) return rc;
     }
-    PMX_BIND(ctx);
+    PMX_HOST_CALL(call, ctx);
     int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    void *d0 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d0))) return rc;
+    Staging node_array;
+    node_array.add(n_nodes, 32);   // the digests, then (tree) every level above them
+    char *d0 = nullptr;
+    if ((rc = call.stage(node_array, &d0))) return rc;
     uint64_t *d_nodes = (uint64_t *)d0;
     // A page-locked matrix is copied from where it lies; a small pageable one goes through the context's page-locked block, a large one
-    // is page-locked for the length of the call (ScopedPin), and what lies between takes the runtime's own staging.
+    // is page-locked for the length of the call, and what lies between takes the runtime's own staging (unasked: its path is the same).
     const char *src = (const char *)matrix;
-    const bool small = bytes <= kSmallCallBytes && !is_pinned(matrix);
-    if (small) {
-        char *h = nullptr;
-        if ((rc = ctx_pinned(ctx, &h))) return rc;
-        std::memcpy(h, matrix, (size_t)bytes);
-        src = h;
+    if (bytes <= kSmallCallBytes) {
+        if (!call.pin(matrix, (size_t)bytes)) {   // (too small to register: the pin only asks)
+            char *h = nullptr;
+            if ((rc = call.pinned_block(&h))) return rc;
+            std::memcpy(h, matrix, (size_t)bytes);
+            src = h;
+        }
+    } else {
+        (void)call.pin(matrix, (size_t)bytes, false);
     }
-    ScopedPin pin(small ? nullptr : matrix, (size_t)bytes);   // (in front of the drain: see pmx_permute_batch)
-    StreamDrain drain{ctx};
-    if ((rc = matrix_leaves_enqueue(ctx, src, n_rows, row_len, layout, d_nodes))) return rc;
+    if ((rc = matrix_leaves_enqueue(call, src, n_rows, row_len, layout, d_nodes))) return rc;
     hipStream_t st = ctx->stream2;
     if (!tree) {
         PMX_HIP(hipMemcpyAsync(leaves_out, d_nodes, n_rows * 32, hipMemcpyDeviceToHost, st));
@@ -1210,8 +1200,8 @@ extern "C" int pmx_matrix_rows(const uint64_t *matrix, size_t n_rows, size_t row
     return PMX_OK;
 }
 
-// k opened rows against the root: their digests by one strided-hash launch (row-major strides), then the climb of
-// pmx_merkle_ragged_verify_paths_dev on the same stream
+// k opened rows against the root: the staged verify body of the Merkle entries (pmx_merkle.cpp: verify_host), which hashes the rows
+// into the leaves by one strided-hash launch in front of the climb
 extern "C" int pmx_matrix_verify_rows(pmx_ctx *ctx, const uint64_t *rows, size_t row_len, const uint64_t *indices, const uint64_t *paths,
                                       size_t depth, uint32_t arity, size_t n_rows, size_t k, const uint64_t root[PMX_LIMBS], uint8_t *ok_out) {
     PMX_ABI_BEGIN("pmx_matrix_verify_rows")
@@ -1224,32 +1214,7 @@ extern "C" int pmx_matrix_verify_rows(pmx_ctx *ctx, const uint64_t *rows, size_t
         return set_error(PMX_ERR_ARG, "depth %zu is not the depth %zu of a tree of arity %u over %zu leaves", depth, tree_depth, arity, n_rows);
     if (int rc = matrix_arity_fits(ctx, arity)) return rc;
     if (k == 0) return PMX_OK;
-    if (k > (SIZE_MAX / 64) / row_len || k > (SIZE_MAX / 64) / (arity + 2) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))) ||
-        k > ((size_t)0x7fffffff * 64) / arity)
-        return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: leaves [k][4] | work [k][(arity + 1) * 4];  slot 1: paths [k][depth][arity - 1][4];  slot 2: root [4] | indices [k];
-    // slot 3: rows [k][row_len][4] | ok [k]
-    const size_t path_bytes = k * depth * (arity - 1) * 32, row_bytes = k * row_len * 32;
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, k * (arity + 2) * 32, &d0))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, path_bytes, &d1))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, 32 + k * 8, &d2))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, row_bytes + k, &d3))) return rc;
-    uint64_t *d_leaves = (uint64_t *)d0, *d_work = d_leaves + k * 4, *d_root = (uint64_t *)d2, *d_idx = d_root + 4, *d_rows = (uint64_t *)d3;
-    uint8_t *d_ok = (uint8_t *)d3 + row_bytes;
-    StreamDrain drain{ctx};
-    hipStream_t st = ctx->stream;
-    PMX_HIP(hipMemcpyAsync(d_rows, rows, row_bytes, hipMemcpyHostToDevice, st));
-    if (path_bytes) PMX_HIP(hipMemcpyAsync(d1, paths, path_bytes, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, st));
-    PMX_HIP(launch_hash_strided(ctx->dev, ctx->t, d_rows, row_len, row_len, 1, d_leaves, 1, k, st));
-    if ((rc = pmx_merkle_ragged_verify_paths_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, n_rows, k, d_root, d_ok, d_work, st))) return rc;
-    PMX_HIP(hipMemcpyAsync(ok_out, d_ok, k, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
-    return PMX_OK;
+    if (k > ((size_t)0x7fffffff * 64) / arity) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    return verify_host(ctx, nullptr, rows, row_len, indices, paths, depth, arity, (uint64_t)n_rows, false, k, root, ok_out);
     PMX_ABI_END
 }

@@ -10,6 +10,7 @@
 
 #include "../../include/poseidon_mi355x.h"
 #include "pmx_internal.hpp"
+#include "pmx_staging.hpp"
 
 struct pmx_ctx {
     int device = 0;
@@ -89,9 +90,6 @@ uint64_t merkle_fixed_piece();
     ::pmx::DeviceGuard device_guard_((ctx)->device);                                 \
     if (device_guard_.err != hipSuccess) return ::pmx::hip_fail(device_guard_.err, "hipSetDevice")
 
-// Grow-only device staging of the host-buffer entry points: at least `bytes` bytes of ctx->scratch[slot] (the caller holds host_lock).
-int ctx_scratch(pmx_ctx *ctx, int slot, size_t bytes, void **out);
-
 // Host-buffer entry points queue asynchronous copies that read and write the CALLER's memory: whatever way they
 // leave (including an error half way through), nothing may still be in flight on the context's streams.
 struct StreamDrain {
@@ -102,6 +100,62 @@ struct StreamDrain {
         (void)hipStreamSynchronize(ctx->stream3);
     }
 };
+
+// A pageable buffer of a large call is page-locked for the length of the call (hipHostRegister: 4.2 ms for the 96 MiB of 2^20 t = 3
+// states, unregister 0.1 ms - profiles/r06/g_host_path_probe.txt) so that it takes the pinned pipeline: 7 ms instead of the 8 ... 20 ms of
+// the runtime's own staging through bounce buffers.
+struct ScopedPin {
+    void *ptr = nullptr;
+    ~ScopedPin() {
+        if (ptr && hipHostUnregister(ptr) != hipSuccess) (void)hipGetLastError();
+    }
+    static constexpr size_t kMinBytes = (size_t)16 << 20;   // below this the registration costs more than it saves
+};
+
+// What a host-buffer call of at most this many bytes stages through: the context's page-locked block, one copy each way.
+constexpr size_t kSmallCallBytes = 64 * 1024;
+
+// The scope of one host-buffer call (pmx_api.cpp has the bodies): made at the top of the entry's body with PMX_HOST_CALL, handed to the
+// helpers that stage for it.  It binds the context's device, holds host_lock and drains the context's streams on the way out.  The
+// MEMBER ORDER is the order of the call's end: the streams are drained first, then the caller's buffers are unregistered, then the
+// lock goes and the caller's device comes back.
+class HostCall {
+public:
+    explicit HostCall(pmx_ctx *c) : ctx(c), guard_(c->device), lock_(c->host_lock), drain_{c} {}
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    hipError_t bind_error() const { return guard_.err; }
+
+    // The next of the context's four grow-only device blocks, at least layout.bytes() long, 16-byte aligned: a block is taken once per
+    // call (asking twice could free what the first asker still holds), so a layout states everything its block carries.  An overflowed
+    // layout and a fifth block are errors.
+    int stage(const Staging &layout, char **base);
+    // the context's page-locked block of kSmallCallBytes, allocated on first use
+    int pinned_block(char **out);
+    // Whether copies from / to [p, p + bytes) may take the chunked pipeline: the buffer was page-locked on entry, or - from
+    // ScopedPin::kMinBytes on - this call has registered it, until the streams are drained.  A registration that fails (locked-memory
+    // limit, a range that is not plain memory) leaves the buffer as it is: false.  An empty buffer holds nothing back.  A caller whose
+    // path does not hang on the answer says so: a buffer too small to register is then not even asked about.
+    bool pin(const void *p, size_t bytes, bool answer_wanted = true);
+
+    pmx_ctx *const ctx;
+
+private:
+    DeviceGuard guard_;
+    std::lock_guard<std::mutex> lock_;
+    ScopedPin pins_[2];
+    StreamDrain drain_;
+    int slots_ = 0, pinned_ = 0;
+};
+
+#define PMX_HOST_CALL(call, ctx)                                                     \
+    ::pmx::HostCall call(ctx);                                                       \
+    if (call.bind_error() != hipSuccess) return ::pmx::hip_fail(call.bind_error(), "hipSetDevice")
+
+// One staged verify body behind pmx_merkle_verify_paths, its arity-k and ragged variants and pmx_matrix_verify_rows (pmx_merkle.cpp).
+// The matrix entry has no leaves: it passes its k opened rows [k][row_len][4], which ride in front of `ok` and are hashed into the leaves.
+int verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *rows, size_t row_len, const uint64_t *indices, const uint64_t *paths,
+                size_t depth, uint32_t arity, uint64_t limit, bool pairs, size_t k, const uint64_t *root, uint8_t *ok_out);
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 

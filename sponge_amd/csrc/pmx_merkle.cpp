@@ -13,7 +13,6 @@
 
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/poseidon_mi355x.h"
@@ -90,14 +89,15 @@ int build_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t total_leaves, uint32_t ari
     PMX_BIND(ctx);
     return levels_dev(ctx, d_nodes, MerkleLevel{0, total_leaves, arity}, n_trees, (hipStream_t)stream);
 }
-// Host buffers (the caller has bound the device): upload the leaves, the levels, download all nodes and / or the last n_trees (the roots).
+// Host buffers: upload the leaves, the levels, download all nodes and / or the last n_trees (the roots).
 int build_host(pmx_ctx *ctx, const uint64_t *leaves, size_t n_trees, size_t total_leaves, size_t n_nodes, uint32_t arity, uint64_t *nodes,
                uint64_t *roots) {
+    PMX_HOST_CALL(call, ctx);
     int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    void *d = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, n_nodes * 32, &d))) return rc;
-    StreamDrain drain{ctx};
+    Staging node_array;
+    node_array.add(n_nodes, 32);   // the leaves, then every level
+    char *d = nullptr;
+    if ((rc = call.stage(node_array, &d))) return rc;
     PMX_HIP(hipMemcpyAsync(d, leaves, total_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = build_dev(ctx, (uint64_t *)d, total_leaves, arity, n_trees, ctx->stream))) return rc;
     if (nodes) PMX_HIP(hipMemcpyAsync(nodes, d, n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -169,34 +169,6 @@ int verify_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices
     PMX_HIP(launch_path_check(cur, d_root, d_indices, limit, d_ok, k, st));
     return PMX_OK;
 }
-// Host buffers: one upload of (leaves, indices, paths, root), `depth` level steps on the device, one download of ok.
-int verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *indices, const uint64_t *paths, size_t depth, uint32_t arity, uint64_t limit,
-                bool pairs, size_t k, const uint64_t *root, uint8_t *ok_out) {
-    if (int rc = arity_fits(ctx, arity)) return rc;
-    if (k == 0) return PMX_OK;
-    if (k > (pairs ? SIZE_MAX / 128 : (SIZE_MAX / 64) / (arity + 2)) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
-        return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: leaves [k][4] | work [k][(arity + 1) * 4];  slot 1: paths [k][depth][arity - 1][4];  slot 2: root [4] | indices [k];  slot 3: ok [k]
-    const size_t path_bytes = k * depth * (arity - 1) * 32;
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, k * (arity + 2) * 32, &d0))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, path_bytes, &d1))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, 32 + k * 8, &d2))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, k, &d3))) return rc;
-    uint64_t *d_leaves = (uint64_t *)d0, *d_work = d_leaves + k * 4, *d_root = (uint64_t *)d2, *d_idx = d_root + 4;
-    StreamDrain drain{ctx};
-    PMX_HIP(hipMemcpyAsync(d_leaves, leaves, k * 32, hipMemcpyHostToDevice, ctx->stream));
-    if (path_bytes) PMX_HIP(hipMemcpyAsync(d1, paths, path_bytes, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = verify_dev(ctx, d_leaves, d_idx, (const uint64_t *)d1, depth, arity, limit, pairs, k, d_root, (uint8_t *)d3, d_work, ctx->stream))) return rc;
-    PMX_HIP(hipMemcpyAsync(ok_out, d3, k, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    return PMX_OK;
-}
 
 // k leaves of a resident tree change: only their ancestors are recomputed, level by level.  While the k updates are fewer than the
 // parents a level has, the level is  gather (the arity children of every update's parent, out of the node array; the bounded twin
@@ -228,6 +200,41 @@ int update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity,
 
 }  // namespace
 
+// Host buffers (pmx_ctx.hpp): one upload of (leaves or rows, paths, root, indices), the rows hashed into the leaves by one strided-hash
+// launch (row-major strides), `depth` level steps on the device, one download of ok.
+int pmx::verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *rows, size_t row_len, const uint64_t *indices, const uint64_t *paths,
+                     size_t depth, uint32_t arity, uint64_t limit, bool pairs, size_t k, const uint64_t *root, uint8_t *ok_out) {
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    Staging climb, siblings, target, verdict;
+    climb.add(k, 32);                                                             // leaves [k][4]
+    const size_t o_work = climb.add(k, (size_t)(arity + 1) * 32);                 // work [k][(arity + 1) * 4]
+    siblings.add(k, depth * (size_t)(arity - 1) * 32);                            // paths [k][depth][arity - 1][4]
+    target.add(1, 32);                                                            // root [4]
+    const size_t o_idx = target.add(k, 8);                                        // indices [k]
+    verdict.add(verdict.times(rows ? k : 0, row_len), 32);                        // rows [k][row_len][4] (the matrix entry)
+    const size_t o_ok = verdict.add(k, 1);                                        // ok [k]
+    // (all four before the first block is touched: the error a caller sees does not depend on which block is too large)
+    if (climb.overflowed() || siblings.overflowed() || target.overflowed() || verdict.overflowed())
+        return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    PMX_HOST_CALL(call, ctx);
+    char *d_climb = nullptr, *d_paths = nullptr, *d_target = nullptr, *d_verdict = nullptr;
+    int rc = PMX_OK;
+    if ((rc = call.stage(climb, &d_climb)) || (rc = call.stage(siblings, &d_paths)) || (rc = call.stage(target, &d_target)) || (rc = call.stage(verdict, &d_verdict))) return rc;
+    uint64_t *d_leaves = (uint64_t *)d_climb, *d_work = (uint64_t *)(d_climb + o_work), *d_root = (uint64_t *)d_target, *d_idx = (uint64_t *)(d_target + o_idx);
+    hipStream_t st = ctx->stream;
+    if (rows) PMX_HIP(hipMemcpyAsync(d_verdict, rows, o_ok, hipMemcpyHostToDevice, st));   // (o_ok: the rows' bytes, a multiple of 32)
+    else PMX_HIP(hipMemcpyAsync(d_leaves, leaves, k * 32, hipMemcpyHostToDevice, st));
+    if (siblings.bytes()) PMX_HIP(hipMemcpyAsync(d_paths, paths, siblings.bytes(), hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(d_root, root, 32, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, st));
+    if (rows) PMX_HIP(launch_hash_strided(ctx->dev, ctx->t, (const uint64_t *)d_verdict, row_len, row_len, 1, d_leaves, 1, k, st));
+    if ((rc = verify_dev(ctx, d_leaves, d_idx, (const uint64_t *)d_paths, depth, arity, limit, pairs, k, d_root, (uint8_t *)(d_verdict + o_ok), d_work, st))) return rc;
+    PMX_HIP(hipMemcpyAsync(ok_out, d_verdict + o_ok, k, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    return PMX_OK;
+}
+
 // ---- 2-to-1 trees and forests: n_leaves a power of two ---------------------------------------------------------------------------
 extern "C" int pmx_merkle_2to1_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, void *stream) {
     if (!ctx || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_dev: null pointer");
@@ -241,9 +248,7 @@ extern "C" int pmx_merkle_2to1(pmx_ctx *ctx, const uint64_t *leaves, size_t n_le
     if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1: null pointer");
     MerkleShape s;
     if (int rc = tree_shape(n_leaves, 2, Family::pairs, &s)) return rc;
-    PMX_BIND(ctx);
-    if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-    return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, 2, nodes, root);
+    return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, 2, nodes, root);   // (tree_shape has refused a node array beyond size_t)
     PMX_ABI_END
 }
 
@@ -260,7 +265,6 @@ extern "C" int pmx_merkle_2to1_forest(pmx_ctx *ctx, const uint64_t *leaves, size
     if (!ctx || !leaves) return set_error(PMX_ERR_ARG, "pmx_merkle_2to1_forest: null pointer");
     size_t total = 0, n_nodes = 0;
     if (int rc = forest_shape(n_trees, leaves_per_tree, 2, Family::pair_forest, &total, &n_nodes)) return rc;
-    PMX_BIND(ctx);
     return build_host(ctx, leaves, n_trees, total, n_nodes, 2, nodes, roots);
     PMX_ABI_END
 }
@@ -289,7 +293,7 @@ extern "C" int pmx_merkle_verify_paths(pmx_ctx *ctx, const uint64_t *leaves, con
         return set_error(PMX_ERR_ARG, "pmx_merkle_verify_paths: null pointer");
     if (int rc = arity_fits(ctx, 2)) return rc;
     if (depth >= 64) return set_error(PMX_ERR_ARG, "depth out of range");
-    return verify_host(ctx, leaves, indices, paths, depth, 2, (uint64_t)1 << depth, true, k, root, ok_out);
+    return verify_host(ctx, leaves, nullptr, 0, indices, paths, depth, 2, (uint64_t)1 << depth, true, k, root, ok_out);
     PMX_ABI_END
 }
 
@@ -315,7 +319,6 @@ extern "C" int pmx_merkle_ary(pmx_ctx *ctx, const uint64_t *leaves, size_t n_lea
     MerkleShape s;
     if (int rc = tree_shape(n_leaves, arity, Family::ary, &s)) return rc;
     if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
     return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, arity, nodes, root);
     PMX_ABI_END
 }
@@ -334,7 +337,6 @@ extern "C" int pmx_merkle_ary_forest(pmx_ctx *ctx, const uint64_t *leaves, size_
     size_t total = 0, n_nodes = 0;
     if (int rc = forest_shape(n_trees, leaves_per_tree, arity, Family::ary_forest, &total, &n_nodes)) return rc;
     if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
     return build_host(ctx, leaves, n_trees, total, n_nodes, arity, nodes, roots);
     PMX_ABI_END
 }
@@ -372,7 +374,7 @@ extern "C" int pmx_merkle_ary_verify_paths(pmx_ctx *ctx, const uint64_t *leaves,
         return set_error(PMX_ERR_ARG, "pmx_merkle_ary_verify_paths: null pointer");
     uint64_t n_leaves = 0;
     if (int rc = shape_error(merkle_leaves_of_depth(arity, depth, &n_leaves), Family::ary)) return rc;
-    return verify_host(ctx, leaves, indices, paths, depth, arity, n_leaves, false, k, root, ok_out);
+    return verify_host(ctx, leaves, nullptr, 0, indices, paths, depth, arity, n_leaves, false, k, root, ok_out);
     PMX_ABI_END
 }
 
@@ -401,16 +403,16 @@ extern "C" int pmx_merkle_ary_update(pmx_ctx *ctx, uint64_t *nodes, size_t n_lea
     const size_t n_rows = plan.n_rows();
     std::vector<uint64_t> digests(n_rows * 4);
     if (n_rows) {
-        PMX_BIND(ctx);
+        PMX_HOST_CALL(call, ctx);
         int rc = PMX_OK;
-        std::lock_guard<std::mutex> lock(ctx->host_lock);
-        // slot 0: rows [n_rows][arity][4] | slots [n_rows];  slot 1: digests [n_rows][4]
-        void *d0 = nullptr, *d1 = nullptr;
-        if ((rc = ctx_scratch(ctx, 0, plan.upload.size() * 8, &d0))) return rc;
-        if ((rc = ctx_scratch(ctx, 1, n_rows * 32, &d1))) return rc;
-        uint64_t *d_rows = (uint64_t *)d0, *d_slots = d_rows + n_rows * arity * 4, *d_dig = (uint64_t *)d1;
-        StreamDrain drain{ctx};
-        PMX_HIP(hipMemcpyAsync(d0, plan.upload.data(), plan.upload.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        Staging children, parents;   // (`children` is plan.upload, byte for byte)
+        children.add(n_rows, (size_t)arity * 32);                 // rows [n_rows][arity][4]
+        const size_t o_slots = children.add(n_rows, 8);           // slots [n_rows]
+        parents.add(n_rows, 32);                                  // digests [n_rows][4]
+        char *d0 = nullptr, *d1 = nullptr;
+        if ((rc = call.stage(children, &d0)) || (rc = call.stage(parents, &d1))) return rc;
+        uint64_t *d_rows = (uint64_t *)d0, *d_slots = (uint64_t *)(d0 + o_slots), *d_dig = (uint64_t *)d1;
+        PMX_HIP(hipMemcpyAsync(d0, plan.upload.data(), children.bytes(), hipMemcpyHostToDevice, ctx->stream));
         for (size_t l = 1; l <= s.depth; ++l) {
             const size_t r = plan.row_first[l], count = plan.level_rows(l);
             PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_rows + r * arity * 4, d_dig + r * 4, arity, count, ctx->stream));
@@ -449,7 +451,6 @@ extern "C" int pmx_merkle_ragged(pmx_ctx *ctx, const uint64_t *leaves, size_t n_
     MerkleShape s;
     if (int rc = tree_shape(n_leaves, arity, Family::ragged, &s)) return rc;
     if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
     return build_host(ctx, leaves, 1, n_leaves, s.n_nodes, arity, nodes, root);
     PMX_ABI_END
 }
@@ -485,7 +486,7 @@ extern "C" int pmx_merkle_ragged_verify_paths(pmx_ctx *ctx, const uint64_t *leav
     if (!ctx || ((!leaves || !indices || !ok_out) && k) || (!paths && k && depth) || !root)
         return set_error(PMX_ERR_ARG, "pmx_merkle_ragged_verify_paths: null pointer");
     if (int rc = ragged_verify_shape(depth, arity, n_leaves)) return rc;
-    return verify_host(ctx, leaves, indices, paths, depth, arity, (uint64_t)n_leaves, false, k, root, ok_out);
+    return verify_host(ctx, leaves, nullptr, 0, indices, paths, depth, arity, (uint64_t)n_leaves, false, k, root, ok_out);
     PMX_ABI_END
 }
 
@@ -512,7 +513,8 @@ int frontier_error(FrontierError e) {
     }
 }
 
-// One piece of the walk (pmx_merkle_frontier.hpp; the caller holds host_lock and has bound the device): one upload of frontier and default
+// One piece of the walk (pmx_merkle_frontier.hpp), a host-buffer call of its own - its host temporaries are declared in front of its
+// scope, so they outlive its drain, and its two blocks grow with the piece: one upload of frontier and default
 // digests, one of the two lists, one of the leaves; the kept nodes and the pads of ALL levels in one launch; one full-row compression
 // launch per level that has rows, on the engine pmx_ctx_engine_info names for its parents; the new frontier and the root gathered in one
 // launch and brought back in one download.  `frontier` ([D][k - 1][4], host) is read in its kept slots and replaced, unused slots zero;
@@ -520,17 +522,19 @@ int frontier_error(FrontierError e) {
 // partial node of every level above the leaves go to their places in the caller's array, one download per level.
 int fixed_piece(pmx_ctx *ctx, const FrontierPlan &P, const uint64_t *defaults, uint64_t *frontier, const uint64_t *leaves, uint64_t *root,
                 uint64_t *nodes, const size_t *first) {
-    int rc = PMX_OK;
     const size_t D = P.depth, fe = P.frontier_elements(), n_place = P.place.size() / 2, n_gather = P.gather.size() / 2;
     std::vector<uint64_t> in((fe + D + 1) * 4), out((fe + 1) * 4), lists(P.place);
     std::memcpy(in.data(), frontier, fe * 32);
     std::memcpy(in.data() + fe * 4, defaults, (D + 1) * 32);
     lists.insert(lists.end(), P.gather.begin(), P.gather.end());
-    void *d0 = nullptr, *d1 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, P.elements * 32, &d0))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, (lists.size() + 2) * 8, &d1))) return rc;
+    PMX_HOST_CALL(call, ctx);
+    Staging rows, pairs;
+    rows.add(P.elements, 32);           // frontier and defaults in | frontier and root out | the rows of the levels (FrontierPlan)
+    pairs.add(lists.size() + 2, 8);     // the place list | the gather list
+    char *d0 = nullptr, *d1 = nullptr;
+    int rc = PMX_OK;
+    if ((rc = call.stage(rows, &d0)) || (rc = call.stage(pairs, &d1))) return rc;
     uint64_t *d = (uint64_t *)d0, *d_lists = (uint64_t *)d1;
-    StreamDrain drain{ctx};
     PMX_HIP(hipMemcpyAsync(d + P.in_frontier * 4, in.data(), in.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     if (!lists.empty()) PMX_HIP(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     if (P.m) PMX_HIP(hipMemcpyAsync(d + (P.level[0].offset + P.level[0].kept) * 4, leaves, (size_t)P.m * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -563,8 +567,6 @@ int fixed_piece(pmx_ctx *ctx, const FrontierPlan &P, const uint64_t *defaults, u
 // m = 0 is one piece that recomputes the partial nodes and the root.  frontier / root: host temporaries, as for fixed_piece.
 int fixed_walk(pmx_ctx *ctx, uint32_t arity, size_t depth, const uint64_t *defaults, uint64_t n, const uint64_t *leaves, uint64_t m,
                uint64_t *frontier, uint64_t *root, uint64_t *nodes, const size_t *first) {
-    PMX_BIND(ctx);
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
     const uint64_t piece = merkle_fixed_piece();
     uint64_t done = 0;
     do {
@@ -585,18 +587,18 @@ extern "C" int pmx_merkle_fixed_defaults(pmx_ctx *ctx, const uint64_t default_le
     u128 capacity = 0;
     if (int rc = frontier_error(frontier_capacity(arity, depth, &capacity))) return rc;
     if (int rc = arity_fits(ctx, arity)) return rc;
-    PMX_BIND(ctx);
-    int rc = PMX_OK;
-    std::lock_guard<std::mutex> lock(ctx->host_lock);
-    // slot 0: e [depth + 1][4] | rows [depth][arity][4];  slot 1: the list that copies e[l] into the arity slots of row l
-    std::vector<uint64_t> list, e((depth + 1) * 4);
+    std::vector<uint64_t> list, e((depth + 1) * 4);     // (in front of the scope: copied from and into until its drain)
     for (size_t l = 0; l < depth; ++l)
         for (uint32_t j = 0; j < arity; ++j) list.push_back(depth + 1 + l * arity + j), list.push_back(l);
-    void *d0 = nullptr, *d1 = nullptr;
-    if ((rc = ctx_scratch(ctx, 0, (depth + 1 + depth * arity) * 32, &d0))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, list.size() * 8, &d1))) return rc;
+    PMX_HOST_CALL(call, ctx);
+    int rc = PMX_OK;
+    Staging digests, copies;
+    digests.add(depth + 1, 32);                  // e [depth + 1][4]
+    digests.add(depth, (size_t)arity * 32);      // rows [depth][arity][4], element depth + 1 on
+    copies.add(list.size(), 8);                  // the list that copies e[l] into the arity slots of row l
+    char *d0 = nullptr, *d1 = nullptr;
+    if ((rc = call.stage(digests, &d0)) || (rc = call.stage(copies, &d1))) return rc;
     uint64_t *d = (uint64_t *)d0, *d_list = (uint64_t *)d1;
-    StreamDrain drain{ctx};
     PMX_HIP(hipMemcpyAsync(d, default_leaf, 32, hipMemcpyHostToDevice, ctx->stream));
     PMX_HIP(hipMemcpyAsync(d_list, list.data(), list.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     for (size_t l = 0; l < depth; ++l) {      // e[l + 1] depends on e[l]: `depth` launches of one unit each
