@@ -886,7 +886,7 @@ extern "C" int pmx_sponge_squeeze_bits_batch(pmx_ctx *ctx, uint64_t *states, uin
 
 // ---- proof-of-work grinding ------------------------------------------------------------------------
 // The smallest nonce v of [first, first + count) with  c = sponge.clone(); c.absorb(&F::from(v)); c.squeeze_bits(bits) all false
-// (mod.rs:232-254, 272-286): one state up, one word down, the candidates exist only in registers (pmx_device.hip: grind_kernel).
+// (mod.rs:232-254, 272-286): one state up, one word down, the candidates exist only in registers (pmx_kernels.hpp: grind_kernel).
 // An Absorbing{rate} or Squeezing sponge permutes before it absorbs (mod.rs:239-252) whatever the nonce: that permutation runs once,
 // on the copy of the state in the context's staging memory, and the search then absorbs at index 0.  The range is walked in chunks
 // (pmx_grind_plan.hpp) of grind_chunk() candidates, the result words read back behind each.

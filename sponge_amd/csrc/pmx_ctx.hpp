@@ -29,7 +29,7 @@ struct pmx_ctx {
     // handed out by pmx_ctx_acquire are shared between sponges (and threads), so those entry points take this lock;
     // the *_dev entry points only read the immutable fields and enqueue on the caller's stream.
     std::mutex host_lock;
-    // Pass lists of the absorb / squeeze drivers that run as passes (pmx_device.hip: sponge_passes): a pool of device blocks, each
+    // Pass lists of the absorb / squeeze drivers that run as passes (pmx_engine_launch.hpp: sponge_passes): a pool of device blocks, each
     // with an event the CONTEXT owns, recorded on the caller's stream behind the last launch that uses the block.  A call takes the
     // block its stream used last (stream order makes that safe while the earlier call is still running), else any block whose event
     // has completed, else a new one; nothing is ever freed or queried through a caller's stream handle on the enqueue path - the

@@ -738,7 +738,7 @@ PMX_FN Abi abi_to_canonical(const Abi &a, const FieldRt &f) {
 }
 
 // The converse of abi_to_canonical for a machine integer: v -> the ABI residue v * 2^256 mod p, fully reduced - what ark-ff's F::from(v)
-// holds (the nonce a grinding search absorbs, pmx_device.hip: grind_kernel).  One Montgomery product of the three limbs of v with
+// holds (the nonce a grinding search absorbs, pmx_kernels.hpp: grind_kernel).  One Montgomery product of the three limbs of v with
 // 2^517 mod p (io + kIoFromU64): v * 2^517 * 2^-261.  T = v * c < 2^64 p gives a norm result below p + 1: one conditional subtraction
 // (fe_to_abi_scaled makes two).
 PMX_FN Abi abi_from_u64(uint64_t v, const FieldRt &f) {

@@ -1,4 +1,4 @@
-// Launcher entry points of pmx_device.hip (host-callable; they only enqueue on `st`).
+// Launcher entry points of pmx_device.hip, pmx_convert.hip and pmx_tree_moves.hip (host-callable; they only enqueue on `st`).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,7 +32,7 @@ hipError_t launch_compress_level(const DevConfig &c, uint32_t t, const uint64_t 
 // is lowered to the smallest nonce whose digest has `bits` low zero bits and best[1] (0 before) is set to 1 with it.  No per-candidate memory.
 hipError_t launch_grind(const DevConfig &c, uint32_t t, const uint64_t *base, uint32_t index, uint32_t bits, uint64_t first, size_t n,
                         uint64_t *best, hipStream_t st);
-// Device scratch for the pass lists of the drivers that run as passes (pmx_device.hip: sponge_passes): `get` hands out at least
+// Device scratch for the pass lists of the drivers that run as passes (pmx_engine_launch.hpp: sponge_passes): `get` hands out at least
 // `bytes` bytes that stay valid for everything enqueued on `st` by this call, `done` is called once behind the call's last launch
 // (pmx_api.cpp: a pool of blocks owned by the context, each released by an event recorded there).  Engines that need no lists
 // call neither.
@@ -61,7 +61,7 @@ constexpr size_t kCutScratchBytes = PMX_SQUEEZE_SCRATCH_BYTES;
 hipError_t launch_squeeze_cut(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index, uint8_t *out, size_t len,
                               bool bits, size_t n, hipStream_t st, const PassScratch &scratch);
 
-// What ONE engine instantiation serves (pmx_device.hip: engine_ops<Engine>() fills it, select_engine picks the table of a call): every
+// What ONE engine instantiation serves (pmx_engine_launch.hpp: engine_ops<Engine>() fills it; pmx_device.hip: select_engine picks the table of a call): every
 // member has the signature of its launch_* above whatever the engine - one that runs absorb / squeeze as per-lane kernels does not touch
 // the PassScratch, one that runs them as passes takes its lists from it.  Both the launchers and describe_launch go through the table
 // select_engine returns, so what pmx_ctx_engine_info reports is what a launch runs.

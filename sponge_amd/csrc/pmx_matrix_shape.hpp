@@ -3,7 +3,7 @@
 // Pure 64-bit arithmetic, host only; compiled into tests/matrix/matrix_host.cpp as well.
 //
 // A matrix has n_rows rows of row_len elements of 32 bytes.  Row-major: element (i, j) at element index i * row_len + j.  Column-major:
-// at j * n_rows + i.  The strided hash kernel (pmx_device.hip: hash_strided_kernel) reads element k of row i at
+// at j * n_rows + i.  The strided hash kernel (pmx_kernels.hpp: hash_strided_kernel) reads element k of row i at
 // i * row_stride + k * elem_stride, so a layout is a pair of strides.
 #pragma once
 #include <cstddef>

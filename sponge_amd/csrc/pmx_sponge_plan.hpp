@@ -1,4 +1,4 @@
-// The absorb / squeeze batch driver as a sequence of wave-uniform PASSES (wide states; pmx_device.hip: sponge_first_kernel,
+// The absorb / squeeze batch driver as a sequence of wave-uniform PASSES (wide states; pmx_kernels.hpp: sponge_first_kernel,
 // permute_listed_kernel, sponge_walk).
 //
 // Reference semantics (file:line in /root/reference):

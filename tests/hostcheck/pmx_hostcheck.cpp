@@ -225,7 +225,7 @@ extern "C" int hc_permute_rt(const pmx_config *cfg, uint64_t *states, size_t n) 
 extern "C" int hc_permute(const pmx_config *cfg, uint64_t *states, size_t n) { return hc_permute_rt(cfg, states, n); }
 
 // op: 0 mul, 1 sqr(a), 2 dot3(a[0..3), b[0..3)), 3 round trip abi->internal->abi, 4 abi_add_mod(a, b),
-//     5 / 6 the per-lane absorb step of the scaled / Montgomery engines (pmx_device.hip: absorb_elements, hash_kernel) and the conversion
+//     5 / 6 the per-lane absorb step of the scaled / Montgomery engines (pmx_kernels.hpp: absorb_elements, hash_kernel) and the conversion
 //     that ends a call without a permutation: to_abi*(fe_normalize(fe_add_lazy(A, from_abi*(b)))), where `a` holds the lane's internal
 //     value A itself as a 256-bit integer (not reduced: up to the 1.3 p of a lane after a permutation) and b is an ABI residue
 extern "C" int hc_field_op(const uint64_t modulus[4], int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
@@ -251,7 +251,7 @@ extern "C" int hc_field_op(const uint64_t modulus[4], int op, const uint64_t *a,
     } else if (op == 3) {
         store_abi(out, fe_to_abi(fe_from_abi(load_abi(a), f), f));
     } else if (op == 4) {
-        // the absorb step of the pass kernels (sponge_walk, AbsorbAdjust): a + b on the ABI residues, no multiplication (pmx_device.hip)
+        // the absorb step of the pass kernels (sponge_walk, AbsorbAdjust): a + b on the ABI residues, no multiplication (pmx_kernels.hpp)
         store_abi(out, abi_add_mod(load_abi(a), load_abi(b), f.io + kIoP32));
     } else if (op == 5) {
         store_abi(out, fe_to_abi_scaled(fe_normalize(fe_add_lazy(limbs_32_to_29(load_abi(a)), fe_from_abi_scaled(load_abi(b)))), f));

@@ -81,7 +81,7 @@ def test_the_rows_are_the_members_of_the_operation_table():
     ops = function_body(source("pmx_launch.hpp"), r"struct EngineOps \{")
     members = re.findall(r"hipError_t \(\*(\w+)\)\(", ops)
     assert tuple(members) == E.ROWS
-    filled = re.search(r"static constexpr EngineOps ops = \{(.*?),\s*&Engine::lds_bytes", source("pmx_device.hip"), re.S).group(1)
+    filled = re.search(r"static constexpr EngineOps ops = \{(.*?),\s*&Engine::lds_bytes", source("pmx_engine_launch.hpp"), re.S).group(1)
     assert tuple(re.findall(r"&L::(\w+)", filled)) == E.ROWS
 
 

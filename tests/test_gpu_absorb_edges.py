@@ -1,7 +1,7 @@
 """Absorbed sums at 0, p, p +- 1 and 2p - 2 on every engine.
 
 Every absorbed element reaches the state through one field addition, `state[capacity + i] += element` (reference
-src/poseidon/mod.rs:128,143).  The per-lane kernels (pmx_device.hip: absorb_elements, hash_kernel) add lazily and only
+src/poseidon/mod.rs:128,143).  The per-lane kernels (pmx_kernels.hpp: absorb_elements, hash_kernel) add lazily and only
 propagate carries - the sum is reduced by the next permutation or, when the call ends without one, by the engine's
 to_abi (fe_to_abi_scaled on QuadEngine / HybridEngine, fe_to_abi on LdsEngine); the pass kernels (sponge_walk,
 AbsorbAdjust) add the ABI residues with one exact conditional subtraction (abi_add_mod).  A random element meets none of

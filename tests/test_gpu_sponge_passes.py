@@ -1,5 +1,5 @@
 """The absorb / squeeze batch driver on wide states (t = 4..9): passes of a wave-uniform permutation kernel
-(sponge_amd/csrc/pmx_sponge_plan.hpp, pmx_device.hip: sponge_first_kernel / permute_listed_kernel) instead of a per-lane state machine, so that the
+(sponge_amd/csrc/pmx_sponge_plan.hpp, pmx_kernels.hpp: sponge_first_kernel / permute_listed_kernel) instead of a per-lane state machine, so that the
 driver runs on the permutation engine of its width - the matrix-core one at t = 7..9.
 
 Reference semantics: absorb src/poseidon/mod.rs:232-254 + absorb_internal :121-150; squeeze_native_field_elements
@@ -127,7 +127,7 @@ def test_wide_driver_other_rate_capacity_splits(rate, capacity):
 
 def test_wide_driver_device_resident_modes_out_of_range_are_clamped():
     """Device-resident mode words are not validated by the host (the host-buffer entry points are): an index above the rate
-    behaves as the rate, exactly as in the per-lane kernels (pmx_device.hip: absorb_kernel).  Through the ABI's own device
+    behaves as the rate, exactly as in the per-lane kernels (pmx_kernels.hpp: absorb_kernel).  Through the ABI's own device
     memory helpers (no torch: this file also runs in a torch-free child process, tests/test_gpu_system_runtime.py)."""
     f, cfg, cr = _config("bn254_fr", None, 254, 8, 5, 8, 57)
     lib = _lib.lib()

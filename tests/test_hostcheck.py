@@ -522,7 +522,7 @@ def _toy_cfg(rate, capacity):
 
 
 def _run_passes(hc, cfg, state, tag, index, squeeze, elems_or_len):
-    """What pmx_device.hip's launch loop + sponge_first_kernel / permute_listed_kernel do for ONE sponge: pass p moves chunk p-1 in memory, then
+    """What the launch loop of pmx_engine_launch.hpp (sponge_passes) + sponge_first_kernel / permute_listed_kernel do for ONE sponge: pass p moves chunk p-1 in memory, then
     permutes where the plan says; the mode words are read-only until the last pass."""
     hc.hc_sponge_pass.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                   ctypes.c_size_t, ctypes.c_void_p]
@@ -617,7 +617,7 @@ def test_absorb_addition_on_abi_residues(hc, p):
 
 @pytest.mark.parametrize("p", [O.BLS12_381_FR, O.BN254_FR, PALLAS, P25519])
 def test_per_lane_absorb_chain_at_its_stated_bounds(hc, p):
-    """The per-lane kernels' `state[capacity + i] += element` (pmx_device.hip: absorb_elements, hash_kernel) and the conversion that
+    """The per-lane kernels' `state[capacity + i] += element` (pmx_kernels.hpp: absorb_elements, hash_kernel) and the conversion that
     ends a call without a permutation: to_abi*(fe_normalize(fe_add_lazy(A, from_abi*(x)))), on the scaled engines (QuadEngine,
     HybridEngine: fe_to_abi_scaled, stated for values below 3 p - a lane after a permutation is below 1.3 p, after one more element
     2.3 p) and on the Montgomery one (LdsEngine: fe_to_abi).  A is the lane's internal value, not reduced, anywhere below 1.3 p; x is a

@@ -2,7 +2,7 @@
 BASELINE configs[1] (t = 3) and configs[2] (t = 9) must keep their occupancy WITHOUT spilling.  A spill does not fail parity - it shows
 up as HBM writes (round 5: an unused branch of the row finish cost the t = 3 kernel 32 bytes of scratch per lane at four waves per
 SIMD and 1.34 x the algorithmic writes, found by the WRITE_SIZE counter pass) - so the budget is pinned here, where every round's CPU
-suite sees it.  `make asm1` compiles ONE kernel (sponge_amd/csrc/Makefile, PMX_TU = 99) in seconds."""
+suite sees it.  `make asm1` compiles ONE kernel (sponge_amd/csrc/Makefile, pmx_device_one.hip) in seconds."""
 import os
 import re
 import shutil

@@ -3,7 +3,7 @@ pmx_merkle_ragged_paths, every refusal that needs no device) and the data fixtur
 runs here; expected values come from the oracles, never from the product: shapes by plain arithmetic, node arrays from the C port level
 by level with the short parent as an absorb of the children that exist (tests/merkle_ragged_oracle.py), the fixture from the Python
 big-integer oracle (tests/golden/make_merkle_ragged_golden.py).  The index arithmetic of the two bounded gather kernels
-(paths_gather_ragged_kernel, node_children_bounded_kernel in sponge_amd/csrc/pmx_device.hip) is restated here lane by lane."""
+(paths_gather_ragged_kernel, node_children_bounded_kernel in sponge_amd/csrc/pmx_tree_moves.hip) is restated here lane by lane."""
 import ctypes
 
 import numpy as np

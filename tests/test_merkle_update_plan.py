@@ -3,7 +3,7 @@
 - The host plan (sponge_amd/csrc/pmx_merkle_plan.hpp) compiled for the host behind tests/merkle_plan/merkle_plan_c.cpp: the device's share
   of pmx_merkle_ary_update - compress the rows of a level, scatter the digests to their slots of the next level's rows - is replayed here
   with the C port's batch hash, and the node array must come out as the C port's full rebuild over the updated leaf row.
-- The index arithmetic of node_scatter_kernel and node_children_kernel (pmx_device.hip) and the level loop of pmx_merkle_ary_update_dev,
+- The index arithmetic of node_scatter_kernel and node_children_kernel (pmx_tree_moves.hip) and the level loop of pmx_merkle_ary_update_dev,
   restated lane by lane, against the same rebuild.
 - The argument checks of both entries that fire before a device is needed.
 - tests/merkle_plan/sanitize_main.cpp, a program of its own, under ASan + UBSan.

@@ -1,4 +1,4 @@
-"""Variable-length rows of the absorb driver, on the CPU: the walk of the ragged pass kernels (sponge_amd/csrc/pmx_device.hip:
+"""Variable-length rows of the absorb driver, on the CPU: the walk of the ragged pass kernels (sponge_amd/csrc/pmx_kernels.hpp:
 sponge_walk, sponge_first_kernel, permute_listed_kernel with RowsRagged) restated over one sponge in tests/varlen_plan/varlen_walk.cpp,
 on the plan and the ragged-row helpers of pmx_sponge_plan.hpp compiled for the host, with the C oracle's permutation.  For every mode
 (tag, index 0..rate) and row length 0..3 rate + 2 at rates 1, 2, 3 and 8 the walk must end with the state and mode words of the

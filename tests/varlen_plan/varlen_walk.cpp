@@ -1,5 +1,5 @@
 // CPU restatement of the absorb side of the pass driver with variable-length rows (test infrastructure, not a product path):
-// the walk of sponge_walk / sponge_first_kernel / permute_listed_kernel in sponge_amd/csrc/pmx_device.hip, over ONE sponge, built on
+// the walk of sponge_walk / sponge_first_kernel / permute_listed_kernel in sponge_amd/csrc/pmx_kernels.hpp, over ONE sponge, built on
 // the plan of pmx_sponge_plan.hpp compiled for the host - absorb_pass, and the helpers the ragged kernels use for a row's length, the
 // empty-row rule and the end of a sponge's walk at its own last pass.  The permutation is the caller's (tests/test_varlen_plan.py: the C oracle), so the
 // test sees the data moved and the permutations performed, in order.

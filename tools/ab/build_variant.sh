@@ -15,12 +15,13 @@ pids=()
 for tu in 0 1 2 3 4; do
   obj=$B/pmx_device_$tu.o
   if [[ " $TUS " == *" $tu "* ]]; then
-    $HIPCC $FLAGS $DEV $EXTRA -DPMX_TU=$tu -c $C/pmx_device.hip -o $obj & pids+=($!)
+    if [ $tu = 0 ]; then unit=$C/pmx_device.hip; else unit="-DPMX_TU=$tu $C/pmx_device_window.hip"; fi
+    $HIPCC $FLAGS $DEV $EXTRA -c $unit -o $obj & pids+=($!)
   else
-    case $tu in 0) src=$C/build/pmx_device.o;; 1) src=$C/build/pmx_device_hyb5.o;; 2) src=$C/build/pmx_device_hybg.o;; 3) src=$C/build/pmx_device_hyb5w.o;; 4) src=$C/build/pmx_device_hybgw.o;; esac
+    if [ $tu = 0 ]; then src=$C/build/pmx_device.o; else src=$C/build/pmx_device_window_$tu.o; fi
     cp $src $obj
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC -shared -fPIC --offload-arch=gfx950 $B/pmx_device_0.o $B/pmx_device_1.o $B/pmx_device_2.o $B/pmx_device_3.o $B/pmx_device_4.o $C/build/pmx_api.o $C/build/pmx_merkle.o $C/build/pmx_mgpu.o $C/build/pmx_params.o -ldl -o $R/tools/ab/libposeidon_$NAME.so
+$HIPCC -shared -fPIC --offload-arch=gfx950 $B/pmx_device_0.o $B/pmx_device_1.o $B/pmx_device_2.o $B/pmx_device_3.o $B/pmx_device_4.o $C/build/pmx_device_window_[5-8].o $C/build/pmx_tree_moves.o $C/build/pmx_convert.o $C/build/pmx_api.o $C/build/pmx_merkle.o $C/build/pmx_mgpu.o $C/build/pmx_hooks.o $C/build/pmx_params.o -ldl -o $R/tools/ab/libposeidon_$NAME.so
 ls -la $R/tools/ab/libposeidon_$NAME.so

@@ -10,14 +10,14 @@ B=$C/build_$NAME
 mkdir -p $B
 HIPCC=/opt/rocm/bin/hipcc
 FLAGS="-O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter --offload-arch=gfx950 -DPMX_MFMA_WINDOW=$K $EXTRA"
-$HIPCC $FLAGS -mllvm -opt-disable=reassociate -DPMX_TU=1 -c $C/pmx_device.hip -o $B/pmx_device_1.o &
-$HIPCC $FLAGS -mllvm -opt-disable=reassociate -DPMX_TU=3 -c $C/pmx_device.hip -o $B/pmx_device_3.o &
+$HIPCC $FLAGS -mllvm -opt-disable=reassociate -DPMX_TU=1 -c $C/pmx_device_window.hip -o $B/pmx_device_1.o &
+$HIPCC $FLAGS -mllvm -opt-disable=reassociate -DPMX_TU=3 -c $C/pmx_device_window.hip -o $B/pmx_device_3.o &
 TU0=$C/build/pmx_device.o
 if [ "${WITH_TU0:-0}" = "1" ]; then   # the public launchers as well (routing experiments)
-  $HIPCC $FLAGS -mllvm -opt-disable=reassociate -DPMX_TU=0 -c $C/pmx_device.hip -o $B/pmx_device_0.o &
+  $HIPCC $FLAGS -mllvm -opt-disable=reassociate -c $C/pmx_device.hip -o $B/pmx_device_0.o &
   TU0=$B/pmx_device_0.o
 fi
 $HIPCC $FLAGS -x hip -c $C/pmx_api.cpp -o $B/pmx_api.o &
 wait
-$HIPCC -shared -fPIC --offload-arch=gfx950 $TU0 $B/pmx_device_1.o $B/pmx_device_3.o $C/build/pmx_device_hybg.o $C/build/pmx_device_hybgw.o $B/pmx_api.o $C/build/pmx_merkle.o $C/build/pmx_mgpu.o $C/build/pmx_params.o -ldl -o $R/tools/ab/libposeidon_$NAME.so
+$HIPCC -shared -fPIC --offload-arch=gfx950 $TU0 $B/pmx_device_1.o $B/pmx_device_3.o $C/build/pmx_device_window_2.o $C/build/pmx_device_window_[4-8].o $C/build/pmx_tree_moves.o $C/build/pmx_convert.o $B/pmx_api.o $C/build/pmx_merkle.o $C/build/pmx_mgpu.o $C/build/pmx_hooks.o $C/build/pmx_params.o -ldl -o $R/tools/ab/libposeidon_$NAME.so
 ls -la $R/tools/ab/libposeidon_$NAME.so
