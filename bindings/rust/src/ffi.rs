@@ -179,6 +179,9 @@ extern "C" {
                             nodes: *mut u64, root: *mut u64) -> c_int;
     pub fn pmx_merkle_fixed_paths(nodes: *const u64, n_leaves: usize, arity: u32, depth: usize, defaults: *const u64, indices: *const u64,
                                   k_paths: usize, paths_out: *mut u64) -> c_int;
+    // k sequential leaf updates of a fixed-depth tree from the openings of the old tree: witnesses, the root after every update, the last root
+    pub fn pmx_merkle_update_witnesses(ctx: *mut pmx_ctx, arity: u32, depth: usize, indices: *const u64, new_leaves: *const u64, paths: *const u64,
+                                       k: usize, witness_out: *mut u64, roots_out: *mut u64, root: *mut u64) -> c_int;
     // device memory for the *_dev entry points
     pub fn pmx_device_alloc(device: c_int, d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn pmx_device_free(device: c_int, d_ptr: *mut c_void) -> c_int;

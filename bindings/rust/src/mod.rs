@@ -341,6 +341,21 @@ impl<F: PrimeField> BatchPoseidon<F> {
                                              core::ptr::null_mut()) });
         nodes
     }
+    /// `indices.len()` sequential leaf updates of a tree of `arity` and fixed `depth` from `paths` (`[k][depth][arity - 1]`), the openings
+    /// of `indices` in the tree before the batch (`pmx_merkle_update_witnesses`): `(witnesses, roots)`, `witnesses[j]` (`[depth][arity - 1]`)
+    /// the opening of `indices[j]` after updates `0 .. j - 1`, `roots[j]` the root after update `j`.  `depth` compression launches.
+    pub fn merkle_update_witnesses(&self, arity: u32, depth: usize, indices: &[u64], new_leaves: &[F], paths: &[F]) -> (Vec<F>, Vec<F>) {
+        let k = indices.len();
+        assert!(arity >= 2, "a parent has at least two children");
+        assert_eq!(new_leaves.len(), k, "one new leaf per index");
+        assert_eq!(paths.len(), k * depth * (arity as usize - 1), "paths is not [k][depth][arity - 1]");
+        let (mut witnesses, mut roots) = (vec![F::zero(); paths.len()], vec![F::zero(); k]);
+        if k > 0 {
+            check(unsafe { ffi::pmx_merkle_update_witnesses(self.ctx.0, arity, depth, indices.as_ptr(), limbs(new_leaves), limbs(paths), k,
+                                                            limbs_mut(&mut witnesses), limbs_mut(&mut roots), core::ptr::null_mut()) });
+        }
+        (witnesses, roots)
+    }
     /// 2-to-1 tree over `leaves` (power of two): all nodes, leaves first, root last.
     pub fn merkle(&self, leaves: &[F]) -> Vec<F> {
         let mut nodes = vec![F::zero(); 2 * leaves.len() - 1];

@@ -510,8 +510,8 @@ int pmx_merkle_ragged_update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leave
  *   level's stored width is e[l].  Every index is checked (< n_leaves) before anything is written.  The paths are accepted unchanged by
  *   pmx_merkle_ary_verify_paths(..., depth, arity, ...): there is no verifier of its own.
  * Like every host-buffer entry these serialise on the context's lock and run inside the catch-all; device scratch is the context's staging.
- * What the family lacks: host buffers only (no *_dev entry and no graph-capturable form), no leaf update of a fixed-depth tree
- *   (pmx_merkle_ary_update on a dense array remains the route), no forest and no device-group form.
+ * What the family lacks: host buffers only (no *_dev entry and no graph-capturable form), no forest and no device-group form.  Leaves of a
+ *   fixed-depth tree are changed by pmx_merkle_update_witnesses below, from their openings; pmx_merkle_ary_update needs the dense array.
  * Errors, nothing launched or written on any: PMX_ERR_ARG for null pointers, arity < 2, depth = 0, depth > 64, k^D beyond 64 bits (k^D =
  *   2^64 is accepted), n_leaves + m > k^D, n_leaves = 0 of a dense tree, byte sizes that overflow size_t; PMX_ERR_CONFIG for arity > rate. */
 int pmx_merkle_fixed_defaults(pmx_ctx *ctx, const uint64_t default_leaf[PMX_LIMBS], uint32_t arity, size_t depth,
@@ -524,6 +524,39 @@ int pmx_merkle_fixed(pmx_ctx *ctx, const uint64_t *leaves, size_t n_leaves, uint
                      uint64_t *nodes /* may be NULL */, uint64_t *root /* may be NULL */);
 int pmx_merkle_fixed_paths(const uint64_t *nodes, size_t n_leaves, uint32_t arity, size_t depth, const uint64_t *defaults,
                            const uint64_t *indices, size_t k_paths, uint64_t *paths_out /* [k_paths][depth][arity - 1][4] */);
+
+/* ---- sequential leaf updates of a fixed-depth tree, with witnesses --------------------------------------
+ * A rollup or state-tree prover holds k updates (indices[j], new_leaves[j]) of a deep, sparsely filled tree and the opening of every
+ * indices[j] in the tree as it stood BEFORE the batch; it needs the root after every update, the witness of every update - the opening of
+ * indices[j] in the tree after updates 0 .. j - 1, which is what a circuit consumes - and the final root.  (No counterpart in the
+ * reference, which has no tree.)
+ * The tree: arity a (2 <= a <= rate), depth D (1 <= D <= 64, a^D <= 2^64), parent = (new; absorb(the a children); squeeze_native(1))[0],
+ *   every row full, exactly as in pmx_merkle_ary: there is no short row.  Openings are [k][D][a - 1][4], bottom-up, per level the siblings
+ *   in child order with the running node's own slot left out: the layout of pmx_merkle_ary_paths (and of pmx_merkle_fixed_paths).
+ * Inputs: indices [k] (duplicates are allowed and are sequential updates of one leaf), new_leaves [k][4], paths [k][D][a - 1][4] - the
+ *   opening of indices[j] in the OLD tree, the one before update 0, the same tree for every j.
+ * The outputs are DEFINED by this model.  An overlay maps (level, node) to a value and starts empty.  For j = 0 .. k - 1, with
+ *   q_l = indices[j] / a^l:  v_0 = new_leaves[j];  for l = 0 .. D - 1 the sibling c of q_l in slot s is overlay[(l, c)] if present, else
+ *   paths[j][l][s] - that value is witness[j][l][s] -, and v_{l+1} is the parent of the row with v_l at digit q_l mod a and the siblings
+ *   around it;  then overlay[(l, q_l)] = v_l for all l <= D, and roots[j] = v_D.
+ *   When `paths` are the true openings of one tree, witness[j] is the true opening of indices[j] in the tree after j updates and roots[j]
+ *   the true root after update j.  The call does NOT check `paths` against an old root: that check is pmx_merkle_ary_verify_paths,
+ *   unchanged (old leaves, indices, paths, D, a, old root).  Inconsistent paths still give exactly the model's bytes.
+ * The work is not sequential by level: once a level is known, the next is k independent compressions.  The host computes, per level, for
+ *   every sibling the last earlier update that wrote it (one sort, then O(k a) per level); per level one gather launch builds the k rows
+ *   and the level's witnesses, and ONE full-row compression launch of k rows follows, on the engine pmx_ctx_engine_info(ctx,
+ *   PMX_OP_COMPRESS, k, a) names (arity 2: the 2-to-1 launch, the quad engine included): D compression launches, k D permutations.  Device
+ *   memory is O(k a) elements whatever D: a level's slab of the openings goes up, and its slab of the witnesses comes down, as one 2-D
+ *   copy, the next level's while this one compresses.
+ * witness_out [k][D][a - 1][4], roots_out [k][4] and root [4] (= roots[k - 1]) may each be NULL; the others receive the same bytes.
+ * k = 0: PMX_OK, nothing launched; a non-NULL root is then PMX_ERR_ARG, because no root exists to return.  k is at most 2^32 - 2.
+ * Host buffers only (no *_dev entry); like every host-buffer entry it serialises on the context's lock and runs inside the catch-all.
+ * Errors, nothing launched or written on any: PMX_ERR_ARG for null pointers, arity < 2, depth = 0, depth > 64, a^D beyond 64 bits (a^D =
+ *   2^64 is accepted), an index >= a^D (the message names it), byte sizes that overflow size_t, k > 2^32 - 2 ("batch too large");
+ *   PMX_ERR_CONFIG for arity > rate. */
+int pmx_merkle_update_witnesses(pmx_ctx *ctx, uint32_t arity, size_t depth, const uint64_t *indices, const uint64_t *new_leaves,
+                                const uint64_t *paths, size_t k, uint64_t *witness_out /* may be NULL: [k][depth][arity - 1][4] */,
+                                uint64_t *roots_out /* may be NULL: [k][4] */, uint64_t *root /* may be NULL: [4], = roots[k - 1] */);
 
 /* ---- matrix commitments: the rows of a trace / LDE matrix as the leaves of a tree ---------------------
  * A prover holds a matrix of n_rows rows and row_len columns, almost always column-major (one column per polynomial), and commits to

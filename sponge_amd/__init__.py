@@ -7,4 +7,4 @@ from .field import BLS12_381_FR, BN254_FR, FIELDS, Field  # noqa: F401
 from .poseidon import (BatchPoseidonSponge, Context, DuplexSpongeMode, PoseidonConfig, PoseidonSponge,  # noqa: F401
                        find_poseidon_ark_and_mds, get_default_poseidon_parameters, pinned_empty,
                        poseidon_config_from_lfsr)
-from .merkle import FixedMerkleTree, IncrementalMerkleTree, MatrixCommitment, MerkleTree, verify_paths, verify_rows  # noqa: F401,E402
+from .merkle import FixedMerkleTree, IncrementalMerkleTree, MatrixCommitment, MerkleTree, update_witnesses, verify_paths, verify_rows  # noqa: F401,E402

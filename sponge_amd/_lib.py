@@ -173,6 +173,7 @@ SIGNATURES = {
     "pmx_merkle_fixed_shape": (ctypes.c_int, [_sz, ctypes.c_uint32, _sz, ctypes.POINTER(_sz)]),
     "pmx_merkle_fixed": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, ctypes.c_uint32, _sz, _u64p, _u64p, _u64p]),
     "pmx_merkle_fixed_paths": (ctypes.c_int, [_u64p, _sz, ctypes.c_uint32, _sz, _u64p, _u64p, _sz, _u64p]),
+    "pmx_merkle_update_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, _sz, _u64p, _u64p, _u64p, _sz, _u64p, _u64p, _u64p]),
     # matrix commitments (layout, arity: uint32_t)
     "pmx_matrix_leaves": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, ctypes.c_uint32, _u64p]),
     "pmx_matrix_commit": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p]),

@@ -120,5 +120,10 @@ hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *i
 // Fixed-depth trees (pmx_merkle_fixed*, pmx_merkle_frontier_append): elems[list[2 i]] = elems[list[2 i + 1]] for i < k, elements of 4 words
 // of one device array, the pairs built by the host (pmx_merkle_frontier.hpp); no destination is a source of the same launch.  k >= 1.
 hipError_t launch_node_place(uint64_t *elems, const uint64_t *list, size_t k, hipStream_t st);
+// Sequential leaf updates (pmx_merkle_update_witnesses), one level: rows[j] = the arity children of update j's parent, cur[j] at digit
+// (indices[j] / pow) % arity and in sibling slot s cur[pred[j][s]] if pred[j][s] < j, else slab[j][s] (slab, wit: [k][arity - 1][4]; pred:
+// [k][arity - 1], pmx_merkle_chain.hpp); the siblings also go to wit[j][s] unless wit is null.  pow = arity^level >= 1, k >= 1.
+hipError_t launch_chain_rows(const uint64_t *cur, const uint64_t *slab, const uint32_t *pred, const uint64_t *indices, uint64_t pow,
+                             uint32_t arity, uint64_t *rows, uint64_t *wit, size_t k, hipStream_t st);
 
 }  // namespace pmx

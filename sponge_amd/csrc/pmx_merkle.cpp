@@ -8,7 +8,8 @@
 // texts, and the order of its checks; the family picks between the twin gather kernels (a ragged entry launches the bounded one whatever
 // the leaf count).  The *_dev entries only enqueue on the caller's stream: no allocation, no synchronisation.  The trees of a fixed depth
 // (pmx_merkle_fixed*, pmx_merkle_frontier_append, at the end of the file) are the same full-row launches over rows that
-// pmx_merkle_frontier.hpp lays out: host buffers only.
+// pmx_merkle_frontier.hpp lays out: host buffers only.  Their sequential leaf updates (pmx_merkle_update_witnesses, last) are `depth` launches
+// of launch_compress_ary over rows a gather kernel chains by pmx_merkle_chain.hpp's plan.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -19,6 +20,7 @@
 #include "pmx_ctx.hpp"
 #include "pmx_internal.hpp"
 #include "pmx_launch.hpp"
+#include "pmx_merkle_chain.hpp"
 #include "pmx_merkle_frontier.hpp"
 #include "pmx_merkle_plan.hpp"
 #include "pmx_merkle_shape.hpp"
@@ -683,6 +685,87 @@ extern "C" int pmx_merkle_fixed_paths(const uint64_t *nodes, size_t n_leaves, ui
             }
         }
     }
+    return PMX_OK;
+    PMX_ABI_END
+}
+
+// ---- sequential leaf updates of a fixed-depth tree, with witnesses ---------------------------------------------------------------------
+// k updates walked level by level (pmx_merkle_chain.hpp): V_0 = new_leaves; per level the planner says which earlier update every sibling
+// comes from, one gather launch builds the k rows (and the level's slab of the witnesses) out of V_l and the level's slab of the old
+// openings, one compression launch of k rows gives V_{l+1}; V_depth is the roots.  Device memory is one block of O(k * arity) elements
+// whatever the depth: V twice, the rows, the indices, and two each of path slab, pred slab and witness slab.  A level's slab goes up and
+// comes down as ONE 2-D copy, (arity - 1) * 32 bytes wide and k high, with the pitch of a whole opening on the host side.
+// Streams: `stream` copies, `stream2` computes.  The slab of level l + 1 goes up behind the gather of level l - 1 (which read its buffer),
+// so it travels while level l compresses; the witness slab of level l comes down on `stream` behind its gather, in front of the next
+// upload - the gather of level l + 2, which writes that buffer again, waits for an upload recorded behind it.  The host plans a
+// level right before it enqueues it, so the plan of level l + 1 can run under the device's level l - as far as the runtime lets it: pred
+// is pageable host memory, [depth][k][arity - 1] for the whole call (only the DEVICE side is O(k * arity) whatever the depth), and a
+// pageable upload may hold the host until the copy stream reaches it.
+extern "C" int pmx_merkle_update_witnesses(pmx_ctx *ctx, uint32_t arity, size_t depth, const uint64_t *indices, const uint64_t *new_leaves,
+                                           const uint64_t *paths, size_t k, uint64_t *witness_out, uint64_t *roots_out, uint64_t *root) {
+    PMX_ABI_BEGIN("pmx_merkle_update_witnesses")
+    if (!ctx || ((!indices || !new_leaves || !paths) && k)) return set_error(PMX_ERR_ARG, "pmx_merkle_update_witnesses: null pointer");
+    u128 capacity = 0;
+    if (int rc = frontier_error(frontier_capacity(arity, depth, &capacity))) return rc;
+    if (k == 0) {
+        if (root) return set_error(PMX_ERR_ARG, "no update leaves no root to return: root must be NULL when k = 0");
+        return PMX_OK;
+    }
+    if (k > kChainMaxUpdates) return set_error(PMX_ERR_ARG, "batch too large: at most %zu updates in one call", kChainMaxUpdates);
+    const size_t sib = arity - 1;
+    Staging opening, block;
+    opening.add(opening.times(opening.times(k, depth), sib), 32);        // paths / witness_out [k][depth][arity - 1][4] (host)
+    const size_t o_v = block.add(block.times(k, 2), 32);                 // V [2][k][4]: the running nodes of a level and of the next
+    const size_t o_rows = block.add(k, (size_t)arity * 32);              // rows [k][arity][4]
+    const size_t o_idx = block.add(k, 8);                                // indices [k]
+    const size_t o_slab = block.add(block.times(k, 2), sib * 32);        // [2] path slabs [k][arity - 1][4]
+    const size_t o_pred = block.add(block.times(k, 2), sib * 4);         // [2] pred slabs [k][arity - 1]
+    const size_t o_wit = block.add(block.times(witness_out ? k : 0, 2), sib * 32);   // [2] witness slabs [k][arity - 1][4]
+    if (opening.overflowed() || block.overflowed()) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
+    const bool all = capacity > (u128)UINT64_MAX;
+    const size_t bad = chain_first_bad(indices, k, (uint64_t)capacity, all);     // (before anything is launched or written)
+    if (bad < k) return set_error(PMX_ERR_ARG, "leaf index %llu out of range", (unsigned long long)indices[bad]);
+    if (int rc = arity_fits(ctx, arity)) return rc;
+    ChainPlanner planner(indices, k, arity);
+    std::vector<uint32_t> pred(depth * k * sib);     // (in front of the scope: copied from until its drain)
+    PMX_HOST_CALL(call, ctx);
+    int rc = PMX_OK;
+    char *d = nullptr;
+    if ((rc = call.stage(block, &d))) return rc;
+    (void)call.pin(paths, opening.bytes(), false);
+    if (witness_out) (void)call.pin(witness_out, opening.bytes(), false);
+    uint64_t *d_v[2] = {(uint64_t *)(d + o_v), (uint64_t *)(d + o_v) + k * 4}, *d_rows = (uint64_t *)(d + o_rows), *d_idx = (uint64_t *)(d + o_idx);
+    const size_t slab_bytes = k * sib * 32, width = sib * 32, pitch = depth * width;
+    hipStream_t copy = ctx->stream, run = ctx->stream2;
+    PMX_HIP(hipMemcpyAsync(d_v[0], new_leaves, k * 32, hipMemcpyHostToDevice, copy));
+    PMX_HIP(hipMemcpyAsync(d_idx, indices, k * 8, hipMemcpyHostToDevice, copy));
+    uint64_t pow = 1;     // arity^l (l < depth: below arity^depth <= 2^64)
+    for (size_t l = 0; l < depth; ++l) {
+        const int slot = (int)(l % pmx_ctx::kPipeChunks);
+        uint32_t *h_pred = pred.data() + l * k * sib;
+        planner.next_level(h_pred);
+        uint64_t *d_slab = (uint64_t *)(d + o_slab + (l & 1) * slab_bytes), *d_wit = witness_out ? (uint64_t *)(d + o_wit + (l & 1) * slab_bytes) : nullptr;
+        uint32_t *d_pred = (uint32_t *)(d + o_pred + (l & 1) * (k * sib * 4));
+        // (the gather of level l - 2 read these buffers: its event is two slots back, recorded before this point)
+        if (l >= 2) PMX_HIP(hipStreamWaitEvent(copy, ctx->pipe_done[(l - 2) % pmx_ctx::kPipeChunks], 0));
+        PMX_HIP(hipMemcpy2DAsync(d_slab, width, (const char *)paths + l * width, pitch, width, k, hipMemcpyHostToDevice, copy));
+        PMX_HIP(hipMemcpyAsync(d_pred, h_pred, k * sib * 4, hipMemcpyHostToDevice, copy));
+        PMX_HIP(hipEventRecord(ctx->pipe_up[slot], copy));
+        PMX_HIP(hipStreamWaitEvent(run, ctx->pipe_up[slot], 0));
+        PMX_HIP(launch_chain_rows(d_v[l & 1], d_slab, d_pred, d_idx, pow, arity, d_rows, d_wit, k, run));
+        PMX_HIP(hipEventRecord(ctx->pipe_done[slot], run));
+        PMX_HIP(launch_compress_ary(ctx->dev, ctx->t, d_rows, d_v[(l + 1) & 1], arity, k, run));
+        if (witness_out) {
+            PMX_HIP(hipStreamWaitEvent(copy, ctx->pipe_done[slot], 0));
+            PMX_HIP(hipMemcpy2DAsync((char *)witness_out + l * width, pitch, d_wit, width, width, k, hipMemcpyDeviceToHost, copy));
+        }
+        if (l + 1 < depth) pow *= arity;
+    }
+    const uint64_t *d_roots = d_v[depth & 1];
+    if (roots_out) PMX_HIP(hipMemcpyAsync(roots_out, d_roots, k * 32, hipMemcpyDeviceToHost, run));
+    if (root) PMX_HIP(hipMemcpyAsync(root, d_roots + (k - 1) * 4, 32, hipMemcpyDeviceToHost, run));
+    PMX_HIP(hipStreamSynchronize(run));
+    PMX_HIP(hipStreamSynchronize(copy));
     return PMX_OK;
     PMX_ABI_END
 }

@@ -1,6 +1,7 @@
 // The data movement of the Merkle entries (pmx_merkle.cpp) around the compression launches: authentication paths, node scatter / gather,
-// the placement lists of the fixed-depth trees.  The kernels move 16-byte pieces of ABI elements and know nothing of a field or an
-// engine, so - like pmx_convert.hip - this translation unit is compiled once.  Declarations: pmx_launch.hpp.
+// the placement lists of the fixed-depth trees, the chained rows of their sequential leaf updates.  The kernels move 16-byte pieces of
+// ABI elements and know nothing of a field or an engine, so - like pmx_convert.hip - this translation unit is compiled once.
+// Declarations: pmx_launch.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -179,6 +180,36 @@ __global__ void __launch_bounds__(256) node_place_kernel(uint4 *elems, const uin
 }
 hipError_t launch_node_place(uint64_t *elems, const uint64_t *list, size_t k, hipStream_t st) {
     return plain(node_place_kernel, k * 2, st, u4(elems), list, k);
+}
+
+// ---- sequential leaf updates of a fixed-depth tree (pmx_merkle_update_witnesses) ------------------------------------------------------
+// One level of k chained updates, pure data movement in front of the level's compression launch: 2 arity lanes per update, one 16-byte
+// half of a child each.  Row j of `rows` is the arity children of update j's parent at this level as update j sees them: its own running
+// node cur[j] at digit (indices[j] / pow) % arity (pow = arity^level), and in sibling slot s the running node cur[pred[j][s]] of the last
+// earlier update that wrote that sibling, or - no such update - slab[j][s], the sibling of the caller's old opening (pmx_merkle_chain.hpp
+// computes pred).  The same lane stores a sibling's piece into wit[j][s] (unless wit is null): the level's slab of the witness.
+// A predecessor is an EARLIER update: whatever pred holds, a value that is not below j (kChainNone among them) reads the slab, so nothing
+// outside cur [k][4] and slab [k][arity - 1][4] is read.
+__global__ void __launch_bounds__(256) chain_rows_kernel(const uint4 *__restrict__ cur, const uint4 *__restrict__ slab,
+                                                         const uint32_t *__restrict__ pred, const uint64_t *__restrict__ indices, uint64_t pow,
+                                                         uint32_t arity, uint4 *__restrict__ rows, uint4 *__restrict__ wit, size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per = 2 * (size_t)arity, j = gid / per;
+    if (j >= k) return;
+    const uint32_t quarter = (uint32_t)(gid - j * per), child = quarter >> 1, half = quarter & 1;
+    const uint32_t digit = (uint32_t)((indices[j] / pow) % arity);
+    if (child == digit) {
+        rows[gid] = cur[j * 2 + half];
+        return;
+    }
+    const size_t slot = j * (arity - 1) + (child < digit ? child : child - 1);
+    const size_t p = pred[slot];
+    const uint4 v = p < j ? cur[p * 2 + half] : slab[slot * 2 + half];
+    rows[gid] = v;
+    if (wit) wit[slot * 2 + half] = v;
+}
+hipError_t launch_chain_rows(const uint64_t *cur, const uint64_t *slab, const uint32_t *pred, const uint64_t *indices, uint64_t pow,
+                             uint32_t arity, uint64_t *rows, uint64_t *wit, size_t k, hipStream_t st) {
+    return plain(chain_rows_kernel, k * 2 * arity, st, u4(cur), u4(slab), pred, indices, pow, arity, u4(rows), u4(wit), k);
 }
 
 hipError_t launch_path_pairs(const uint64_t *cur, const uint64_t *paths, const uint64_t *indices, size_t depth, size_t level,

@@ -520,4 +520,21 @@ inline std::vector<Fp> merkle_fixed(const PoseidonConfig &parameters, const std:
     return nodes;
 }
 
+// k sequential leaf updates of a tree of `arity` and fixed `depth` from `paths` [k][depth][arity - 1], the openings of `indices` in the tree
+// before the batch (pmx_merkle_update_witnesses): witnesses[j] ([depth][arity - 1]) is the opening of indices[j] after updates 0 .. j - 1,
+// roots[j] the root after update j.  `depth` compression launches whatever k.
+struct MerkleUpdateWitnesses {
+    std::vector<Fp> witnesses, roots;
+};
+inline MerkleUpdateWitnesses merkle_update_witnesses(const PoseidonConfig &parameters, size_t depth, const std::vector<uint64_t> &indices,
+                                                     const std::vector<Fp> &new_leaves, const std::vector<Fp> &paths, uint32_t arity = 2, int device = 0) {
+    const size_t k = indices.size();
+    if (arity < 2 || new_leaves.size() != k || paths.size() != k * depth * (arity - 1)) throw std::invalid_argument("new_leaves are [k], paths [k][depth][arity - 1]");
+    MerkleUpdateWitnesses out{std::vector<Fp>(paths.size()), std::vector<Fp>(k)};
+    if (k)
+        check(pmx_merkle_update_witnesses(parameters.context(device)->get(), arity, depth, indices.data(), new_leaves[0].l.data(), paths[0].l.data(), k,
+                                          out.witnesses[0].l.data(), out.roots[0].l.data(), nullptr));
+    return out;
+}
+
 }  // namespace pmx_host

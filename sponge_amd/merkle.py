@@ -208,6 +208,16 @@ class IncrementalMerkleTree:
         return self._root
 
 
+def update_witnesses(parameters: PoseidonConfig, depth: int, indices, new_leaves, paths, arity: int = 2, device: int = 0):
+    """k sequential leaf updates of a tree of `arity` and fixed `depth` (a rollup's state tree) from the openings of the k indices in the
+    tree BEFORE the batch, paths [k][depth][arity - 1][4] as FixedMerkleTree.open gives them (pmx_merkle_update_witnesses; `depth`
+    compression launches of k rows whatever k).  Returns (witnesses, roots): witnesses[j] [depth][arity - 1][4] is the opening of
+    indices[j] in the tree after updates 0 .. j - 1, roots[j] [4] the root after update j; roots[-1] is the final root.  Duplicate
+    indices are sequential updates of one leaf.  The paths are not checked against an old root: that is verify_paths."""
+    wit, roots, _ = parameters.context(device).merkle_update_witnesses(arity, depth, indices, new_leaves, paths)
+    return wit, roots
+
+
 def verify_paths(parameters: PoseidonConfig, leaves: np.ndarray, indices, paths: np.ndarray, root: np.ndarray,
                  device: int = 0, arity: int = 2, n_leaves: int = None) -> np.ndarray:
     """k authentication paths at once: leaves [k][4], indices [k], paths [k][depth][4] -> bool[k]

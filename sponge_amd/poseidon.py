@@ -493,6 +493,24 @@ class Context:
         _lib.check(_lib.lib().pmx_merkle_fixed(self._h, _ptr(leaves), leaves.shape[0], arity, depth, _ptr(defaults), _ptr(nodes), _ptr(root)))
         return nodes, root
 
+    def merkle_update_witnesses(self, arity: int, depth: int, indices, new_leaves, paths, want_witnesses: bool = True, want_roots: bool = True,
+                                want_root: bool = False):
+        """k sequential leaf updates of a fixed-depth tree from the openings `paths` [k][depth][arity - 1][4] of `indices` in the tree before
+        the batch (pmx_merkle_update_witnesses): (witnesses [k][depth][arity - 1][4], roots [k][4], root [4]), each None unless wanted.
+        witnesses[j] is the opening of indices[j] after updates 0 .. j - 1, roots[j] the root after update j."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = idx.shape[0]
+        new = np.ascontiguousarray(new_leaves, dtype=np.uint64).reshape(-1, 4)
+        paths = np.ascontiguousarray(paths, dtype=np.uint64)
+        assert new.shape[0] == k, "one new leaf per index"
+        assert paths.size == k * depth * (arity - 1) * 4, "paths are [k][depth][arity - 1][4]"
+        wit = np.zeros((k, depth, arity - 1, 4), dtype=np.uint64) if want_witnesses else None
+        roots = np.zeros((k, 4), dtype=np.uint64) if want_roots else None
+        root = np.zeros(4, dtype=np.uint64) if want_root else None
+        _lib.check(_lib.lib().pmx_merkle_update_witnesses(self._h, arity, depth, _ptr(idx) if k else None, _ptr(new) if k else None,
+                                                          _ptr(paths) if k else None, k, _ptr(wit), _ptr(roots), _ptr(root)))
+        return wit, roots, root
+
     # ---- matrix commitments: `matrix` is the flat element array [n_rows * row_len][4] in the given layout (a pointer-sized int: a raw
     # host address, page-locked memory of pmx_host_alloc for instance) ---------
     def matrix_leaves(self, matrix, n_rows: int, row_len: int, layout: int) -> np.ndarray:
