@@ -42,6 +42,9 @@
  * uint32_t) 4 bytes, d_offsets and d_indices (uint64_t) 8 bytes, d_ok (uint8_t) any address.  Nothing beyond these is assumed: buffers
  * carved out of one allocation at base + 16 k are as good as allocations of their own, and a call writes nothing outside the arrays
  * it is documented to write (tests/test_gpu_footprint.py).  The host-buffer entry points accept any host pointer.
+ *
+ * Refused calls (host-buffer entry points): every argument is validated before anything is staged, so a call that returns PMX_ERR_ARG
+ * has launched nothing and has written no byte of any of the caller's arrays (tests/test_gpu_host_footprint.py).
  */
 #ifndef POSEIDON_MI355X_H
 #define POSEIDON_MI355X_H
