@@ -683,7 +683,9 @@ int pmx_mgpu_permute_gather_dev(pmx_mgpu *g, uint64_t *const *d_shards, uint64_t
  * all-gathered into d_top[local] = [2*world-1][4], which then receives the top levels, root last (world = 1: [1][4]).
  * Only enqueues. */
 int pmx_mgpu_merkle_2to1_dev(pmx_mgpu *g, uint64_t *const *d_nodes, uint64_t *const *d_top, size_t n_leaves);
-/* Host leaves [n_leaves][4] -> root [4] (single-process groups). */
+/* Host leaves [n_leaves][4] -> root [4] (single-process groups).  A host-buffer entry on every local device at once: it holds each
+ * slot's context for the length of the call, as pmx_mgpu_permute_batch does, and its device staging (a subtree and the top levels per
+ * slot) is kept by the group's contexts, grow-only, until the group is destroyed. */
 int pmx_mgpu_merkle_2to1(pmx_mgpu *g, const uint64_t *leaves, size_t n_leaves, uint64_t *root);
 
 /* (Test hooks of the device-group code - fault injection in the host fan-out, device groups whose slots share one GPU, a

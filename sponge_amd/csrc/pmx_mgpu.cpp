@@ -19,10 +19,12 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <string>
 #include <system_error>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/poseidon_mi355x.h"
@@ -45,22 +47,15 @@ struct pmx_mgpu {
 // whole single-device ABI - neither needs librccl nor pays for mapping it.  dlopen by SONAME: a process that already
 // holds a copy (PyTorch bundles one) gets that copy.
 namespace {
+// the entry points the table binds, in the order they are looked up: member `Name` is nccl`Name`, with the type rccl.h declares
+#define PMX_RCCL_ENTRIES(X)                                                                                              \
+    X(GetVersion) X(GetUniqueId) X(CommInitAll) X(CommInitRank) X(CommDestroy) X(CommCount) X(CommUserRank) X(AllGather) \
+    X(Broadcast) X(Send) X(Recv) X(GroupStart) X(GroupEnd) X(GetErrorString)
 struct Rccl {
     void *handle = nullptr;
-    ncclResult_t (*GetVersion)(int *) = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t *, int, const int *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int *) = nullptr;
-    ncclResult_t (*CommUserRank)(const ncclComm_t, int *) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Broadcast)(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
+#define X(name) decltype(&nccl##name) name = nullptr;
+    PMX_RCCL_ENTRIES(X)
+#undef X
     std::string error;
 };
 
@@ -94,20 +89,9 @@ Rccl &rccl_lib() {
             if (!p && r->error.empty()) r->error = std::string("librccl has no symbol ") + name;
             return p;
         };
-        r->GetVersion = (decltype(r->GetVersion))sym("ncclGetVersion");
-        r->GetUniqueId = (decltype(r->GetUniqueId))sym("ncclGetUniqueId");
-        r->CommInitAll = (decltype(r->CommInitAll))sym("ncclCommInitAll");
-        r->CommInitRank = (decltype(r->CommInitRank))sym("ncclCommInitRank");
-        r->CommDestroy = (decltype(r->CommDestroy))sym("ncclCommDestroy");
-        r->CommCount = (decltype(r->CommCount))sym("ncclCommCount");
-        r->CommUserRank = (decltype(r->CommUserRank))sym("ncclCommUserRank");
-        r->AllGather = (decltype(r->AllGather))sym("ncclAllGather");
-        r->Broadcast = (decltype(r->Broadcast))sym("ncclBroadcast");
-        r->Send = (decltype(r->Send))sym("ncclSend");
-        r->Recv = (decltype(r->Recv))sym("ncclRecv");
-        r->GroupStart = (decltype(r->GroupStart))sym("ncclGroupStart");
-        r->GroupEnd = (decltype(r->GroupEnd))sym("ncclGroupEnd");
-        r->GetErrorString = (decltype(r->GetErrorString))sym("ncclGetErrorString");
+#define X(name) r->name = (decltype(r->name))sym("nccl" #name);
+        PMX_RCCL_ENTRIES(X)
+#undef X
         return r;
     }();
     return *lib;
@@ -130,6 +114,20 @@ static int rccl_fail(ncclResult_t r, const char *what) {
         ncclResult_t r_ = (expr);                             \
         if (r_ != ncclSuccess) return rccl_fail(r_, #expr);   \
     } while (0)
+
+// PMX_OK, or the failure of the RCCL call `what`
+static int rccl_status(ncclResult_t r, const char *what) { return r == ncclSuccess ? PMX_OK : rccl_fail(r, what); }
+
+// One grouped call: ncclGroupStart, `post`, ncclGroupEnd - which is always reached once the group is open.  `post` returns at its first
+// failure, a local one (HIP, an argument) or a refused post under its RCCL name (rccl_status); that is what the call reports, and
+// ncclGroupEnd's own failure only behind a post that went through.
+template <class Post>
+static int grouped(Post post) {
+    PMX_RCCL(rccl_lib().GroupStart());
+    const int rc = post();
+    const ncclResult_t e = rccl_lib().GroupEnd();
+    return rc ? rc : rccl_status(e, "ncclGroupEnd");
+}
 
 extern "C" int pmx_shard_bounds(size_t n, int world, int rank, size_t *start, size_t *count) {
     if (world <= 0 || rank < 0 || rank >= world || !start || !count) return set_error(PMX_ERR_ARG, "pmx_shard_bounds: bad argument");
@@ -165,18 +163,23 @@ static void group_free(pmx_mgpu *g) {
 // owns a group under construction: whatever way the constructor leaves (error code or exception), the half-built group
 // is torn down unless release() was reached
 struct GroupHolder {
-    pmx_mgpu *g;
+    pmx_mgpu *g = nullptr;
     ~GroupHolder() { if (g) group_free(g); }
     pmx_mgpu *release() { pmx_mgpu *r = g; g = nullptr; return r; }
 };
 
-static int group_contexts(pmx_mgpu *g, const pmx_config *cfg) {
-    for (size_t l = 0; l < g->device.size(); ++l) {
-        pmx_ctx *c = nullptr;
-        int rc = pmx_ctx_create(cfg, g->device[l], &c);
-        if (rc) return rc;
-        g->ctx[l] = c;
-    }
+// The half-built group both creators start from, under `hold`: ranks first_rank ... of `world` on `devices`, a context per slot, no
+// communicator yet.
+static int group_make(GroupHolder &hold, const pmx_config *cfg, int world, int first_rank, std::vector<int> devices) {
+    pmx_mgpu *g = hold.g = new (std::nothrow) pmx_mgpu();
+    if (!g) return set_error(PMX_ERR_HOST, "out of host memory");
+    g->world = world;
+    g->first_rank = first_rank;
+    g->device = std::move(devices);
+    g->ctx.assign(g->device.size(), nullptr);
+    g->comm.assign(g->device.size(), nullptr);
+    for (size_t l = 0; l < g->device.size(); ++l)
+        if (int rc = pmx_ctx_create(cfg, g->device[l], &g->ctx[l])) return rc;
     g->t = (uint32_t)pmx_ctx_width(g->ctx[0]);
     return PMX_OK;
 }
@@ -230,25 +233,17 @@ extern "C" int pmx_mgpu_create(const pmx_config *cfg, int n_devices, const int *
     const int max_slots = shared || visible > PMX_MAX_LOCAL_DEVICES ? PMX_MAX_LOCAL_DEVICES : visible;
     if (n_devices <= 0 || n_devices > max_slots) return set_error(PMX_ERR_ARG, "n_devices %d out of range [1,%d]", n_devices, max_slots);
     if (shared && !devices) return set_error(PMX_ERR_ARG, "shared-device groups (test hook) name their devices explicitly");
-    GroupHolder hold{new (std::nothrow) pmx_mgpu()};
-    pmx_mgpu *g = hold.g;
-    if (!g) return set_error(PMX_ERR_HOST, "out of host memory");
-    g->world = n_devices;
-    g->first_rank = 0;
-    g->device.resize(n_devices);
-    g->ctx.assign(n_devices, nullptr);
-    g->comm.assign(n_devices, nullptr);
+    std::vector<int> list(n_devices);
     for (int l = 0; l < n_devices; ++l) {
-        const int d = devices ? devices[l] : l;
-        g->device[l] = d;
+        const int d = list[l] = devices ? devices[l] : l;
         if (d < 0 || d >= visible) return set_error(PMX_ERR_ARG, "device %d out of range [0,%d)", d, visible);
         for (int k = 0; k < l && !shared; ++k)
-            if (g->device[k] == d) return set_error(PMX_ERR_ARG, "device %d listed twice", d);
+            if (list[k] == d) return set_error(PMX_ERR_ARG, "device %d listed twice", d);
     }
-    int rc = group_contexts(g, cfg);
-    if (rc) return rc;
-    ncclResult_t r = rccl_lib().CommInitAll(g->comm.data(), n_devices, g->device.data());
-    if (r != ncclSuccess) return rccl_fail(r, "ncclCommInitAll");
+    GroupHolder hold;
+    if (int rc = group_make(hold, cfg, n_devices, 0, std::move(list))) return rc;
+    pmx_mgpu *g = hold.g;
+    if (int rc = rccl_status(rccl_lib().CommInitAll(g->comm.data(), n_devices, g->device.data()), "ncclCommInitAll")) return rc;
     *out = hold.release();
     return PMX_OK;
     PMX_ABI_END
@@ -264,23 +259,14 @@ extern "C" int pmx_mgpu_create_rank(const pmx_config *cfg, int device, int rank,
     if (visible == 0) return set_error(PMX_ERR_HIP, "no HIP device available; this library has no CPU fallback");
     if (device < 0 || device >= visible) return set_error(PMX_ERR_ARG, "device %d out of range [0,%d)", device, visible);
     if (int rc = rccl_ready()) return rc;
-    GroupHolder hold{new (std::nothrow) pmx_mgpu()};
-    pmx_mgpu *g = hold.g;
-    if (!g) return set_error(PMX_ERR_HOST, "out of host memory");
-    g->world = world;
-    g->first_rank = rank;
-    g->device.assign(1, device);
-    g->ctx.assign(1, nullptr);
-    g->comm.assign(1, nullptr);
-    int rc = group_contexts(g, cfg);
-    if (rc) return rc;
+    GroupHolder hold;
+    if (int rc = group_make(hold, cfg, world, rank, {device})) return rc;
     ncclUniqueId u;
     std::memcpy(u.internal, id, PMX_UNIQUE_ID_BYTES);
     {
         DeviceGuard guard(device);
         if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
-        ncclResult_t r = rccl_lib().CommInitRank(&g->comm[0], world, u, rank);
-        if (r != ncclSuccess) return rccl_fail(r, "ncclCommInitRank");
+        if (int rc = rccl_status(rccl_lib().CommInitRank(&hold.g->comm[0], world, u, rank), "ncclCommInitRank")) return rc;
     }
     *out = hold.release();
     return PMX_OK;
@@ -336,20 +322,51 @@ extern "C" int pmx_mgpu_synchronize(pmx_mgpu *g) {
     PMX_ABI_END
 }
 
-static int local_span(const pmx_mgpu *g, size_t n_total, size_t l, size_t *start, size_t *count) {
-    return pmx_shard_bounds(n_total, g->world, g->first_rank + (int)l, start, count);
+// piece i of `chunks` of a shard of `count` units
+static void piece_span(size_t count, int chunks, int i, size_t *first, size_t *cnt) {
+    const size_t lo = count / (size_t)chunks * (size_t)i + count % (size_t)chunks * (size_t)i / (size_t)chunks;
+    const size_t hi = count / (size_t)chunks * (size_t)(i + 1) + count % (size_t)chunks * (size_t)(i + 1) / (size_t)chunks;
+    *first = lo;
+    *cnt = hi - lo;
+}
+
+// `count` units from unit `start` on.  Every rank derives every rank's span, and every piece of it, from (n_total, world, chunks, i) alone.
+struct Span {
+    size_t start = 0, count = 0;
+    // piece i of `chunks` of this span, counted from the span's own first unit
+    Span piece(int chunks, int i) const {
+        Span p;
+        piece_span(count, chunks, i, &p.start, &p.count);
+        return p;
+    }
+};
+// the shard of `rank` (one of the communicator's, so pmx_shard_bounds has nothing to refuse) / of local slot l
+static Span rank_span(const pmx_mgpu *g, size_t n_total, int rank) {
+    Span s;
+    (void)pmx_shard_bounds(n_total, g->world, rank, &s.start, &s.count);
+    return s;
+}
+static Span slot_span(const pmx_mgpu *g, size_t n_total, size_t l) { return rank_span(g, n_total, g->first_rank + (int)l); }
+
+// the two conditions more than one entry states
+static int single_process(const pmx_mgpu *g, const char *who) {
+    if ((int)g->ctx.size() != g->world)
+        return set_error(PMX_ERR_ARG, "%s needs a single-process group (this one holds %zu of %d ranks)", who, g->ctx.size(), g->world);
+    return PMX_OK;
+}
+static int sharded_tree_shape(const pmx_mgpu *g, size_t n_leaves) {
+    const size_t W = (size_t)g->world;
+    if (W & (W - 1)) return set_error(PMX_ERR_ARG, "the sharded tree needs a power-of-two number of ranks (have %d)", g->world);
+    if (n_leaves == 0 || (n_leaves & (n_leaves - 1)) || n_leaves < W) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two >= the number of ranks");
+    return PMX_OK;
 }
 
 // ---- permutation ---------------------------------------------------------------------------------------------------
 extern "C" int pmx_mgpu_permute_shards_dev(pmx_mgpu *g, uint64_t *const *d_shards, size_t n_total) {
     PMX_ABI_BEGIN("pmx_mgpu_permute_shards_dev")
     if (!g || !d_shards) return set_error(PMX_ERR_ARG, "pmx_mgpu_permute_shards_dev: null pointer");
-    for (size_t l = 0; l < g->ctx.size(); ++l) {
-        size_t start = 0, count = 0;
-        int rc = local_span(g, n_total, l, &start, &count);
-        if (rc) return rc;
-        if ((rc = pmx_permute_batch_dev(g->ctx[l], d_shards[l], count, g->ctx[l]->stream))) return rc;   // no collective on the data path
-    }
+    for (size_t l = 0; l < g->ctx.size(); ++l)   // no collective on the data path
+        if (int rc = pmx_permute_batch_dev(g->ctx[l], d_shards[l], slot_span(g, n_total, l).count, g->ctx[l]->stream)) return rc;
     return PMX_OK;
     PMX_ABI_END
 }
@@ -359,8 +376,7 @@ extern "C" int pmx_mgpu_permute_shards_dev(pmx_mgpu *g, uint64_t *const *d_shard
 // also for pageable memory, whose copies block the calling thread.  `work(l, start, count)` runs on device l's thread.
 template <class Work>
 static int fan_out(pmx_mgpu *g, size_t n, const char *who, Work work) {
-    if ((int)g->ctx.size() != g->world)
-        return set_error(PMX_ERR_ARG, "%s needs a single-process group (this one holds %zu of %d ranks)", who, g->ctx.size(), g->world);
+    if (int rc = single_process(g, who)) return rc;
     if (n == 0) return PMX_OK;
     const size_t L = g->ctx.size();
     std::vector<int> rcs(L, PMX_OK);
@@ -370,14 +386,13 @@ static int fan_out(pmx_mgpu *g, size_t n, const char *who, Work work) {
     auto run = [&](size_t l) noexcept {
         int rc = PMX_OK;
         try {
-            size_t start = 0, count = 0;
-            rc = local_span(g, n, l, &start, &count);
-            if (!rc && count) {
+            const Span s = slot_span(g, n, l);
+            if (s.count) {
 #ifdef PMX_TEST_HOOKS
                 if (hook_fail_local() == (int)l) rc = set_error(PMX_ERR_HIP, "injected failure (pmx_mgpu_test_fault)");
                 else
 #endif
-                    rc = work(l, start, count);
+                    rc = work(l, s.start, s.count);
             }
             if (rc) msgs[l] = pmx_last_error();   // the error text is thread-local: carry it back to the caller's thread
         } catch (...) {
@@ -440,95 +455,63 @@ extern "C" int pmx_mgpu_all_gather_dev(pmx_mgpu *g, const uint64_t *const *d_sha
     if (n_total > SIZE_MAX / (row_elems * 32)) return set_error(PMX_ERR_ARG, "gather byte size overflows size_t");
     const size_t words = row_elems * 4;   // u64 words per unit
     const bool equal = n_total % (size_t)g->world == 0;
-    PMX_RCCL(rccl_lib().GroupStart());
-    ncclResult_t r = ncclSuccess;
-    for (size_t l = 0; l < g->ctx.size() && r == ncclSuccess; ++l) {
-        DeviceGuard guard(g->device[l]);
-        hipStream_t st = g->ctx[l]->stream;
-        if (equal) {
-            r = rccl_lib().AllGather(d_shards[l], d_all[l], (n_total / (size_t)g->world) * words, ncclUint64, g->comm[l], st);
-        } else {
-            for (int root = 0; root < g->world && r == ncclSuccess; ++root) {
-                size_t start = 0, count = 0;
-                (void)pmx_shard_bounds(n_total, g->world, root, &start, &count);
-                if (count == 0) continue;
+    return grouped([&]() -> int {
+        for (size_t l = 0; l < g->ctx.size(); ++l) {
+            DeviceGuard guard(g->device[l]);
+            hipStream_t st = g->ctx[l]->stream;
+            if (equal) {
+                if (int rc = rccl_status(rccl_lib().AllGather(d_shards[l], d_all[l], (n_total / (size_t)g->world) * words, ncclUint64, g->comm[l], st), "ncclAllGather")) return rc;
+                continue;
+            }
+            for (int root = 0; root < g->world; ++root) {
+                const Span s = rank_span(g, n_total, root);
+                if (s.count == 0) continue;
+                uint64_t *into = d_all[l] + s.start * words;
                 const bool mine = root == g->first_rank + (int)l;
-                r = rccl_lib().Broadcast(mine ? (const void *)d_shards[l] : (const void *)(d_all[l] + start * words), d_all[l] + start * words,
-                                  count * words, ncclUint64, root, g->comm[l], st);
+                if (int rc = rccl_status(rccl_lib().Broadcast(mine ? d_shards[l] : into, into, s.count * words, ncclUint64, root, g->comm[l], st), "ncclBroadcast")) return rc;
             }
         }
-    }
-    ncclResult_t e = rccl_lib().GroupEnd();
-    if (r != ncclSuccess) return rccl_fail(r, equal ? "ncclAllGather" : "ncclBroadcast");
-    if (e != ncclSuccess) return rccl_fail(e, "ncclGroupEnd");
-    return PMX_OK;
+        return PMX_OK;
+    });
     PMX_ABI_END
 }
 
 // ---- gather to one rank, and the gather piece by piece behind the last step ---------------------------------------------
-// piece i of `chunks` of a shard of `count` units
-static void piece_span(size_t count, int chunks, int i, size_t *first, size_t *cnt) {
-    const size_t lo = count / (size_t)chunks * (size_t)i + count % (size_t)chunks * (size_t)i / (size_t)chunks;
-    const size_t hi = count / (size_t)chunks * (size_t)(i + 1) + count % (size_t)chunks * (size_t)(i + 1) / (size_t)chunks;
-    *first = lo;
-    *cnt = hi - lo;
-}
-
-// Inside an open group: the transfers of piece i of every shard, on the slots' first or second stream.  root >= 0: every other
-// rank's piece goes to `root` (one ncclSend per rank, world - 1 ncclRecv on the root); root < 0: to every rank.  A rank that receives
-// also copies its own piece into its copy of the result.  Every rank derives every other rank's piece from (n_total, world, chunks, i)
-// alone, so the sends and the receives of a pair always agree.
+// The transfers of piece i of every shard, on the slots' first or second stream (inside an open group, unless there is nobody to talk
+// to).  root >= 0: every other rank's piece goes to `root` (one ncclSend per rank, world - 1 ncclRecv on the root); root < 0: to every
+// rank.  A rank that receives also copies its own piece into its copy of the result.  The sends and the receives of a pair agree
+// because both sides take the piece from Span.
 static int post_piece(pmx_mgpu *g, const uint64_t *const *d_shards, uint64_t *const *d_all, size_t n_total, size_t words, int root, int chunks, int i,
-                      bool second_stream, ncclResult_t *nr, const char **what) {
+                      bool second_stream) {
     for (size_t l = 0; l < g->ctx.size(); ++l) {
         const int me = g->first_rank + (int)l;
         const bool i_receive = root < 0 || root == me;
         DeviceGuard guard(g->device[l]);
         if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
         hipStream_t st = second_stream ? g->ctx[l]->stream2 : g->ctx[l]->stream;
-        size_t start = 0, count = 0, pf = 0, pc = 0;
-        (void)pmx_shard_bounds(n_total, g->world, me, &start, &count);
-        piece_span(count, chunks, i, &pf, &pc);
-        const uint64_t *mine = d_shards[l] + pf * words;
-        if (i_receive && pc && d_all[l] + (start + pf) * words != mine)
-            PMX_HIP(hipMemcpyAsync(d_all[l] + (start + pf) * words, mine, pc * words * 8, hipMemcpyDeviceToDevice, st));
+        const Span shard = rank_span(g, n_total, me), p = shard.piece(chunks, i);
+        const uint64_t *mine = d_shards[l] + p.start * words;
+        if (i_receive && p.count && d_all[l] + (shard.start + p.start) * words != mine)
+            PMX_HIP(hipMemcpyAsync(d_all[l] + (shard.start + p.start) * words, mine, p.count * words * 8, hipMemcpyDeviceToDevice, st));
         for (int peer = 0; peer < g->world; ++peer) {
             if (peer == me) continue;
-            if ((root < 0 || root == peer) && pc) {
-                *nr = rccl_lib().Send(mine, pc * words, ncclUint64, peer, g->comm[l], st);
-                if (*nr != ncclSuccess) { *what = "ncclSend"; return PMX_OK; }
-            }
-            if (i_receive) {
-                size_t qs = 0, qn = 0, qf = 0, qc = 0;
-                (void)pmx_shard_bounds(n_total, g->world, peer, &qs, &qn);
-                piece_span(qn, chunks, i, &qf, &qc);
-                if (qc) {
-                    *nr = rccl_lib().Recv(d_all[l] + (qs + qf) * words, qc * words, ncclUint64, peer, g->comm[l], st);
-                    if (*nr != ncclSuccess) { *what = "ncclRecv"; return PMX_OK; }
-                }
-            }
+            if ((root < 0 || root == peer) && p.count)
+                if (int rc = rccl_status(rccl_lib().Send(mine, p.count * words, ncclUint64, peer, g->comm[l], st), "ncclSend")) return rc;
+            if (!i_receive) continue;
+            const Span theirs = rank_span(g, n_total, peer), q = theirs.piece(chunks, i);
+            if (q.count)
+                if (int rc = rccl_status(rccl_lib().Recv(d_all[l] + (theirs.start + q.start) * words, q.count * words, ncclUint64, peer, g->comm[l], st), "ncclRecv")) return rc;
         }
     }
     return PMX_OK;
 }
 
-// one group: GroupStart, the piece, GroupEnd - with the error of whichever call failed first
+// one piece as one grouped call
 static int gather_piece(pmx_mgpu *g, const uint64_t *const *d_shards, uint64_t *const *d_all, size_t n_total, size_t words, int root, int chunks, int i,
                         bool second_stream) {
-    if (g->world == 1) {   // nobody to talk to: the copy of the own piece is all there is (and RCCL is not entered with an empty group)
-        ncclResult_t nr = ncclSuccess;
-        const char *what = "";
-        return post_piece(g, d_shards, d_all, n_total, words, root, chunks, i, second_stream, &nr, &what);
-    }
-    PMX_RCCL(rccl_lib().GroupStart());
-    ncclResult_t nr = ncclSuccess;
-    const char *what = "";
-    const int rc = post_piece(g, d_shards, d_all, n_total, words, root, chunks, i, second_stream, &nr, &what);
-    const ncclResult_t e = rccl_lib().GroupEnd();
-    if (rc) return rc;
-    if (nr != ncclSuccess) return rccl_fail(nr, what);
-    if (e != ncclSuccess) return rccl_fail(e, "ncclGroupEnd");
-    return PMX_OK;
+    // world 1: nobody to talk to, the copy of the own piece is all there is (and RCCL is not entered with an empty group)
+    if (g->world == 1) return post_piece(g, d_shards, d_all, n_total, words, root, chunks, i, second_stream);
+    return grouped([&] { return post_piece(g, d_shards, d_all, n_total, words, root, chunks, i, second_stream); });
 }
 
 static int gather_args(const pmx_mgpu *g, const void *d_shards, uint64_t *const *d_all, int root, const char *who) {
@@ -563,12 +546,10 @@ extern "C" int pmx_mgpu_permute_gather_dev(pmx_mgpu *g, uint64_t *const *d_shard
     const size_t words = (size_t)g->t * 4;
     for (int i = 0; i < chunks; ++i) {
         for (size_t l = 0; l < g->ctx.size(); ++l) {
-            size_t start = 0, count = 0, pf = 0, pc = 0;
-            int rc = local_span(g, n_total, l, &start, &count);
-            if (rc) return rc;
-            piece_span(count, chunks, i, &pf, &pc);
+            const Span p = slot_span(g, n_total, l).piece(chunks, i);
             pmx_ctx *c = g->ctx[l];
-            if (pc && (rc = pmx_permute_batch_dev(c, d_shards[l] + pf * words, pc, c->stream))) return rc;
+            if (p.count)
+                if (int rc = pmx_permute_batch_dev(c, d_shards[l] + p.start * words, p.count, c->stream)) return rc;
             PMX_BIND(c);
             PMX_HIP(hipEventRecord(c->pipe_done[i], c->stream));
             PMX_HIP(hipStreamWaitEvent(c->stream2, c->pipe_done[i], 0));
@@ -591,10 +572,8 @@ extern "C" int pmx_mgpu_permute_gather_dev(pmx_mgpu *g, uint64_t *const *d_shard
 extern "C" int pmx_mgpu_merkle_2to1_dev(pmx_mgpu *g, uint64_t *const *d_nodes, uint64_t *const *d_top, size_t n_leaves) {
     PMX_ABI_BEGIN("pmx_mgpu_merkle_2to1_dev")
     if (!g || !d_nodes || !d_top) return set_error(PMX_ERR_ARG, "pmx_mgpu_merkle_2to1_dev: null pointer");
-    const size_t W = (size_t)g->world;
-    if (W & (W - 1)) return set_error(PMX_ERR_ARG, "the sharded tree needs a power-of-two number of ranks (have %d)", g->world);
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1)) || n_leaves < W) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two >= the number of ranks");
-    const size_t m = n_leaves / W;
+    if (int rc = sharded_tree_shape(g, n_leaves)) return rc;
+    const size_t W = (size_t)g->world, m = n_leaves / W;
     for (size_t l = 0; l < g->ctx.size(); ++l) {
         int rc = pmx_merkle_2to1_dev(g->ctx[l], d_nodes[l], m, g->ctx[l]->stream);
         if (rc) return rc;
@@ -604,15 +583,14 @@ extern "C" int pmx_mgpu_merkle_2to1_dev(pmx_mgpu *g, uint64_t *const *d_nodes, u
         PMX_HIP(hipMemcpyAsync(d_top[0], d_nodes[0] + (2 * m - 2) * 4, 32, hipMemcpyDeviceToDevice, g->ctx[0]->stream));
         return PMX_OK;
     }
-    PMX_RCCL(rccl_lib().GroupStart());
-    ncclResult_t r = ncclSuccess;
-    for (size_t l = 0; l < g->ctx.size() && r == ncclSuccess; ++l) {
-        DeviceGuard guard(g->device[l]);
-        r = rccl_lib().AllGather(d_nodes[l] + (2 * m - 2) * 4, d_top[l], 4, ncclUint64, g->comm[l], g->ctx[l]->stream);
-    }
-    ncclResult_t e = rccl_lib().GroupEnd();
-    if (r != ncclSuccess) return rccl_fail(r, "ncclAllGather");
-    if (e != ncclSuccess) return rccl_fail(e, "ncclGroupEnd");
+    const auto roots = [&]() -> int {
+        for (size_t l = 0; l < g->ctx.size(); ++l) {
+            DeviceGuard guard(g->device[l]);
+            if (int rc = rccl_status(rccl_lib().AllGather(d_nodes[l] + (2 * m - 2) * 4, d_top[l], 4, ncclUint64, g->comm[l], g->ctx[l]->stream), "ncclAllGather")) return rc;
+        }
+        return PMX_OK;
+    };
+    if (int rc = grouped(roots)) return rc;
     for (size_t l = 0; l < g->ctx.size(); ++l) {
         int rc = pmx_merkle_2to1_dev(g->ctx[l], d_top[l], W, g->ctx[l]->stream);
         if (rc) return rc;
@@ -621,42 +599,47 @@ extern "C" int pmx_mgpu_merkle_2to1_dev(pmx_mgpu *g, uint64_t *const *d_nodes, u
     PMX_ABI_END
 }
 
-// Host leaves, single-process groups.  root: [4].
+// One call scope per local slot (pmx_ctx.hpp: HostCall, which neither copies nor moves - a deque constructs in place), entered in slot
+// order and left in the reverse order, so that the device the caller had current comes back last.  Nobody else takes two of these
+// locks: the fan-out's worker threads hold their own slot's only, and in a shared-device test group every slot still has a context,
+// and so a lock, of its own.
+struct SlotCalls {
+    std::deque<HostCall> calls;
+    // the scope of the next slot; a device that cannot be bound fails the way PMX_HOST_CALL does
+    int enter(pmx_ctx *c) {
+        calls.emplace_back(c);
+        if (calls.back().bind_error() != hipSuccess) return hip_fail(calls.back().bind_error(), "hipSetDevice");
+        return PMX_OK;
+    }
+    ~SlotCalls() { while (!calls.empty()) calls.pop_back(); }
+};
+
+// Host leaves, single-process groups.  root: [4].  A host-buffer entry like pmx_merkle_2to1, on every slot's context at once: each slot
+// stages one block - its subtree `nodes` [2m - 1][4], then `top` [2W - 1][4] - which its context keeps (grow-only) until the group is
+// destroyed; the scopes hold the slots' host locks, and on every way out they drain the streams before the locks go.
 extern "C" int pmx_mgpu_merkle_2to1(pmx_mgpu *g, const uint64_t *leaves, size_t n_leaves, uint64_t *root) {
     PMX_ABI_BEGIN("pmx_mgpu_merkle_2to1")
     if (!g || !leaves || !root) return set_error(PMX_ERR_ARG, "pmx_mgpu_merkle_2to1: null pointer");
-    if ((int)g->ctx.size() != g->world)
-        return set_error(PMX_ERR_ARG, "pmx_mgpu_merkle_2to1 needs a single-process group (this one holds %zu of %d ranks)", g->ctx.size(), g->world);
-    const size_t W = (size_t)g->world, L = g->ctx.size();
-    if (W & (W - 1)) return set_error(PMX_ERR_ARG, "the sharded tree needs a power-of-two number of ranks (have %d)", g->world);
-    if (n_leaves == 0 || (n_leaves & (n_leaves - 1)) || n_leaves < W) return set_error(PMX_ERR_ARG, "n_leaves must be a power of two >= the number of ranks");
+    if (int rc = single_process(g, "pmx_mgpu_merkle_2to1")) return rc;
+    if (int rc = sharded_tree_shape(g, n_leaves)) return rc;
     if (n_leaves > SIZE_MAX / 64) return set_error(PMX_ERR_ARG, "tree byte size overflows size_t");
-    const size_t m = n_leaves / W;
-    std::vector<uint64_t *> d_nodes(L, nullptr), d_top(L, nullptr);
-    int rc = PMX_OK;
-    auto cleanup = [&]() {
-        (void)pmx_mgpu_synchronize(g);
-        for (size_t l = 0; l < L; ++l) {
-            DeviceGuard guard(g->device[l]);
-            if (d_nodes[l]) (void)hipFree(d_nodes[l]);
-            if (d_top[l]) (void)hipFree(d_top[l]);
-        }
-    };
-    for (size_t l = 0; l < L && !rc; ++l) {
-        DeviceGuard guard(g->device[l]);
-        hipError_t e = hipMalloc((void **)&d_nodes[l], (2 * m - 1) * 32);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_top[l], (2 * W - 1) * 32);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_nodes[l], leaves + (size_t)l * m * 4, m * 32, hipMemcpyHostToDevice, g->ctx[l]->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "pmx_mgpu_merkle_2to1: device staging");
+    const size_t W = (size_t)g->world, m = n_leaves / W;
+    Staging block;
+    const size_t nodes_at = block.add(2 * m - 1, 32), top_at = block.add(2 * W - 1, 32);
+    std::vector<uint64_t *> d_nodes(W, nullptr), d_top(W, nullptr);
+    SlotCalls slots;
+    for (size_t l = 0; l < W; ++l) {   // (the slot's device is current from its scope on)
+        char *d = nullptr;
+        int rc = slots.enter(g->ctx[l]);
+        if (rc || (rc = slots.calls.back().stage(block, &d))) return rc;
+        d_nodes[l] = (uint64_t *)(d + nodes_at);
+        d_top[l] = (uint64_t *)(d + top_at);
+        PMX_HIP(hipMemcpyAsync(d_nodes[l], leaves + l * m * 4, m * 32, hipMemcpyHostToDevice, g->ctx[l]->stream));
     }
-    if (!rc) rc = pmx_mgpu_merkle_2to1_dev(g, d_nodes.data(), d_top.data(), n_leaves);
-    if (!rc) {
-        DeviceGuard guard(g->device[0]);
-        hipError_t e = hipMemcpyAsync(root, d_top[0] + (W == 1 ? 0 : (2 * W - 2) * 4), 32, hipMemcpyDeviceToHost, g->ctx[0]->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g->ctx[0]->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "pmx_mgpu_merkle_2to1: root copy");
-    }
-    cleanup();
-    return rc;
+    if (int rc = pmx_mgpu_merkle_2to1_dev(g, d_nodes.data(), d_top.data(), n_leaves)) return rc;
+    PMX_BIND(g->ctx[0]);
+    PMX_HIP(hipMemcpyAsync(root, d_top[0] + (W == 1 ? 0 : (2 * W - 2) * 4), 32, hipMemcpyDeviceToHost, g->ctx[0]->stream));
+    PMX_HIP(hipStreamSynchronize(g->ctx[0]->stream));
+    return PMX_OK;
     PMX_ABI_END
 }

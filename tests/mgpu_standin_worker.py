@@ -473,10 +473,32 @@ def main():
                                               ctypes.c_void_p(np.zeros(4, dtype=np.uint64).ctypes.data))
                 assert rc == _lib.PMX_ERR_ARG and b"power-of-two number of ranks" in lib.pmx_last_error()
                 return "world is not a power of two: refused"
-            for log2_m in (0, 1, 7, 12):
-                m = world << log2_m
-                leaves = synth.random_elements(cfg.field, m, seed=0x5EED0068 + log2_m)
-                assert np.array_equal(g.merkle_root(leaves), cr.merkle(leaves, threads=0)[-1]), f"root of {m} leaves"
+            trees = {}                                           # the C restatement's tree per size, computed once
+
+            def tree(log2_m):
+                if log2_m not in trees:
+                    leaves = np.ascontiguousarray(synth.random_elements(cfg.field, world << log2_m, seed=0x5EED0068 + log2_m), dtype=np.uint64).reshape(-1, 4)
+                    trees[log2_m] = leaves, cr.merkle(leaves, threads=0)[-1]
+                return trees[log2_m]
+
+            # ascending, then the largest again, the smallest and one in between: the staging blocks the slots' contexts keep are by
+            # then larger than the call needs
+            for log2_m in (0, 1, 7, 12, 12, 0, 7):
+                leaves, want = tree(log2_m)
+                assert np.array_equal(g.merkle_root(leaves), want), f"root of {world << log2_m} leaves"
+            # an all-gather that fails inside the host entry: the status comes back, and the call has left no lock held, nothing in
+            # flight and the blocks usable - the next tree and the next host batch on the same group are right
+            leaves, want = tree(1)
+            got = np.zeros(4, dtype=np.uint64)
+            fake.fake_rccl_fail(1, 1)
+            rc = lib.pmx_mgpu_merkle_2to1(g._h, ctypes.c_void_p(leaves.ctypes.data), leaves.shape[0], ctypes.c_void_p(got.ctypes.data))
+            msg = lib.pmx_last_error().decode()
+            fake.fake_rccl_fail(0, 0)
+            assert rc == _lib.PMX_ERR_RCCL and "ncclAllGather" in msg, (rc, msg)
+            assert np.array_equal(g.merkle_root(leaves), want), "root after the refused call"
+            n = world * 3 + 1
+            states = synth.random_elements(cfg.field, n * T, seed=0x5EED006A).reshape(n, T, 4)
+            assert np.array_equal(g.permute_batch(states), cr.permute_batch(states, threads=0)), "host batch after the refused call"
             for bad in (0, world // 2, 3 * world):
                 rc = lib.pmx_mgpu_merkle_2to1(g._h, ctypes.c_void_p(np.zeros((max(bad, 1), 4), dtype=np.uint64).ctypes.data), bad,
                                               ctypes.c_void_p(np.zeros(4, dtype=np.uint64).ctypes.data))
@@ -634,7 +656,7 @@ def main():
             assert lib.pmx_mgpu_get_info(None, None) == _lib.PMX_ERR_ARG and lib.pmx_mgpu_synchronize(None) == _lib.PMX_ERR_ARG
             assert lib.pmx_mgpu_destroy(None) == _lib.PMX_OK
             bad_cfg = S.poseidon.c_config(cfg)
-            bad_cfg.rate = 0                                            # group_contexts fails: the half-built group is torn down
+            bad_cfg.rate = 0                                            # group_make fails: the half-built group is torn down
             arr = (ctypes.c_int * world)(*([0] * world))
             assert lib.pmx_mgpu_create(ctypes.byref(bad_cfg), world, arr, ctypes.byref(h)) == _lib.PMX_ERR_CONFIG and not h.value
             assert lib.pmx_mgpu_create_rank(ctypes.byref(bad_cfg), 0, 0, 1, uid, ctypes.byref(h)) == _lib.PMX_ERR_CONFIG
