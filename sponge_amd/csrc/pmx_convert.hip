@@ -144,9 +144,10 @@ hipError_t launch_squeeze_cut(const DevConfig &c, uint32_t t, uint64_t *states, 
     size_t per = kCutScratchBytes / (elems * 32);
     if (per == 0) per = 1;
     if (per > n) per = n;
-    uint32_t *block = nullptr;
-    hipError_t e = scratch.get(scratch.owner, st, per * elems * 32, &block);
+    PassLease lease(scratch, st);   // given back behind the last conversion launch
+    hipError_t e = lease.take(per * elems * 32);
     if (e != hipSuccess) return e;
+    uint32_t *block = lease.block;
     FieldRt f = c.field;
     f.io = c.consts + c.io_offset;
     for (size_t first = 0; first < n && e == hipSuccess; first += per) {
@@ -160,7 +161,6 @@ hipError_t launch_squeeze_cut(const DevConfig &c, uint32_t t, uint64_t *states, 
                            block, dst, f, total, (uint32_t)elems, (uint64_t)len, unit);
         e = hipGetLastError();
     }
-    scratch.done(scratch.owner, st, block);
     return e;
 }
 

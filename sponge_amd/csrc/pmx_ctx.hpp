@@ -1,4 +1,5 @@
-// Private definition of pmx_ctx and the helpers shared by pmx_api.cpp (one device), pmx_merkle.cpp (the trees) and pmx_mgpu.cpp (device groups).
+// Private definition of pmx_ctx and the helpers shared by the entries of one device (pmx_context.cpp, pmx_host_call.cpp, pmx_batch.cpp,
+// pmx_sponge.cpp, pmx_matrix.cpp), pmx_merkle.cpp (the trees) and pmx_mgpu.cpp (device groups).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,12 +73,12 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
-// Candidates per launch of pmx_sponge_grind (pmx_api.cpp).  Defined in pmx_hooks.cpp, the object that exists in a shipped and a test
+// Candidates per launch of pmx_sponge_grind (pmx_sponge.cpp).  Defined in pmx_hooks.cpp, the object that exists in a shipped and a test
 // build: the measured constant in the shipped library; the test build lets pmx_test_grind_chunk (include/poseidon_mi355x_testing.h)
 // replace it, so that a test can put a hit into the third chunk without an oracle leg of two product chunks, and the chunk sweep can
 // take every size through the product's own host loop.
 uint64_t grind_chunk();
-// Rows per upload slab of the matrix entries (pmx_api.cpp), the same way: 0 in the shipped library - the slab is then what
+// Rows per upload slab of the matrix entries (pmx_matrix.cpp), the same way: 0 in the shipped library - the slab is then what
 // PMX_MATRIX_SLAB_BYTES of device memory holds (pmx_matrix_shape.hpp: matrix_slab_rows) - or what pmx_test_matrix_slab_rows set, so that
 // a matrix of a few hundred rows takes the multi-slab path and the slab sweep runs every size through the product's own host loop.
 uint64_t matrix_slab_rows_hook();
@@ -115,7 +116,7 @@ struct ScopedPin {
 // What a host-buffer call of at most this many bytes stages through: the context's page-locked block, one copy each way.
 constexpr size_t kSmallCallBytes = 64 * 1024;
 
-// The scope of one host-buffer call (pmx_api.cpp has the bodies): made at the top of the entry's body with PMX_HOST_CALL, handed to the
+// The scope of one host-buffer call (pmx_host_call.cpp has the bodies): made at the top of the entry's body with PMX_HOST_CALL, handed to the
 // helpers that stage for it.  It binds the context's device, holds host_lock and drains the context's streams on the way out.  The
 // MEMBER ORDER is the order of the call's end: the streams are drained first, then the caller's buffers are unregistered, then the
 // lock goes and the caller's device comes back.
@@ -158,5 +159,14 @@ int verify_host(pmx_ctx *ctx, const uint64_t *leaves, const uint64_t *rows, size
                 size_t depth, uint32_t arity, uint64_t limit, bool pairs, size_t k, const uint64_t *root, uint8_t *ok_out);
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// The launch-grid bound: the most units (states, rows, sponges, compressions) an entry hands to one launch, a grid of 2^31 - 1
+// workgroups of 64 units.  What the entries test behind "batch too large".
+constexpr size_t kMaxLaunchUnits = (size_t)0x7fffffff * 64;
+// The argument helpers the batch, sponge and matrix entries share (pmx_host_call.cpp):
+// n * elems_per_row * 32 bytes, or an error if that does not fit size_t / the launch grid
+int batch_bytes(size_t n, size_t elems_per_row, size_t *bytes);
+// the argument lines the batch *_dev entries share, in the order each of them tests them (a null pointer counts as aligned)
+int dev_batch_args(const void *a, const void *b, size_t n);
 
 }  // namespace pmx

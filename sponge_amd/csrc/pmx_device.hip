@@ -139,15 +139,15 @@ hipError_t launch_absorb_varlen(const DevConfig &c, uint32_t t, uint64_t *states
 hipError_t launch_hash_varlen(const DevConfig &c, uint32_t t, const uint64_t *in, const uint64_t *offsets, size_t max_len, uint64_t *out,
                               size_t out_len, size_t n, hipStream_t st, const PassScratch &scratch) {
     const size_t st_bytes = n * t * 32, words = (n + 3) / 4 * 4;   // (the mode words start 16-byte aligned)
-    uint32_t *block = nullptr;
-    hipError_t e = scratch.get(scratch.owner, st, st_bytes + 2 * words * 4, &block);
+    PassLease lease(scratch, st);   // given back behind the squeeze, the last launch that reads the block
+    hipError_t e = lease.take(st_bytes + 2 * words * 4);
     if (e != hipSuccess) return e;
+    uint32_t *block = lease.block;
     uint64_t *states = reinterpret_cast<uint64_t *>(block);
     uint32_t *tag = block + st_bytes / 4, *index = tag + words;
     e = hipMemsetAsync(block, 0, st_bytes + 2 * words * 4, st);
     if (e == hipSuccess) e = launch_absorb_varlen(c, t, states, tag, index, in, offsets, max_len, n, st, scratch);
     if (e == hipSuccess) e = launch_squeeze(c, t, states, tag, index, out, out_len, n, st, scratch);
-    scratch.done(scratch.owner, st, block);   // behind the squeeze, the last launch that reads the block
     return e;
 }
 

@@ -96,6 +96,7 @@ struct Launch {
         if (n > 0xffffffffull || len > kSpongeMaxLen) return hipErrorInvalidValue;
         const uint32_t last = (uint32_t)(passes - 1);    // (no sponge permutes in the last pass)
         const size_t launches = pass_launches(passes);
+        PassLease lease(provider, st);                   // given back behind the last launch that reads the lists
         uint32_t *scratch = nullptr;                     // [counters, padded to 64 words | list A: n | list B: n]
         const size_t head = (passes + 63) / 64 * 64;
         hipError_t e = hipSuccess;
@@ -103,9 +104,8 @@ struct Launch {
         if (launches > 1) {                              // a second permutation is possible: its sponges travel on a list
             // (NOT hipMallocAsync / hipFreeAsync: with several contexts - several streams - alive, ROCm 7.0's stream-ordered pool
             // handed out blocks whose earlier use was still in flight; tools/soak.py lost sponges and took a memory fault that way)
-            e = provider.get(provider.owner, st, (head + 2 * n) * 4, &scratch);
-            if (e != hipSuccess) return e;
-            // (from here on every way out passes provider.done: the block is released by the event recorded there)
+            if (lease.take((head + 2 * n) * 4) != hipSuccess) return lease.err;
+            scratch = lease.block;
             lists[0] = scratch + head;
             lists[1] = scratch + head + n;
             e = hipMemsetAsync(scratch, 0, head * 4, st);
@@ -116,7 +116,6 @@ struct Launch {
         if (e == hipSuccess) e = enqueue(first, c, t, n, st, states, tag, index, io, rows, n, last, lists[1], scratch ? scratch + 1 : nullptr);
         for (uint32_t p = 1; p < launches && e == hipSuccess; ++p)
             e = enqueue(listed, c, t, n, st, states, tag, index, io, rows, p, last, lists[p & 1], scratch + p, lists[(p + 1) & 1], scratch + p + 1);
-        if (scratch && provider.done) provider.done(provider.owner, st, scratch);   // behind the last launch that reads the lists
         return e;
     }
     // what a launch of `op` would run on (pmx_ctx_engine_info): filled by the engine, completed per kernel family here

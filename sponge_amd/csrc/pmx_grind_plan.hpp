@@ -1,4 +1,4 @@
-// The host walk of a proof-of-work search (pmx_sponge_grind, pmx_api.cpp): the nonce range [first, first + count) is searched in
+// The host walk of a proof-of-work search (pmx_sponge_grind, pmx_sponge.cpp): the nonce range [first, first + count) is searched in
 // chunks of at most `chunk` candidates, one launch each, in ascending order, and the walk stops behind the first chunk that reports a
 // hit - every nonce of an earlier chunk is smaller than every nonce of a later one, so that chunk's minimum is the range's.
 // Pure 64-bit arithmetic, host only; compiled into tests/grind/grind_host.cpp as well.

@@ -9,7 +9,7 @@
 #include "pmx_launch.hpp"
 
 namespace pmx {
-// Candidates per launch of pmx_sponge_grind (pmx_api.cpp), chosen from the sweep of profiles/grind/README.md.
+// Candidates per launch of pmx_sponge_grind (pmx_sponge.cpp), chosen from the sweep of profiles/grind/README.md.
 static constexpr uint64_t kGrindChunk = (uint64_t)1 << 21;
 // Leaves per piece of pmx_merkle_frontier_append / pmx_merkle_fixed (pmx_merkle.cpp); how it was chosen: profiles/merkle_fixed/README.md.
 static constexpr uint64_t kMerkleFixedPiece = (uint64_t)1 << 22;
@@ -44,7 +44,7 @@ uint64_t pmx::merkle_fixed_piece() {
 extern "C" int pmx_test_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
                                           uint64_t *d_leaves, void *stream) {
     if (!ctx || !d_matrix || !d_leaves) return pmx::set_error(PMX_ERR_ARG, "pmx_test_matrix_leaves_dev: null pointer");
-    if (n_rows == 0 || row_len == 0 || n_rows > (size_t)0x7fffffff * 64) return pmx::set_error(PMX_ERR_ARG, "pmx_test_matrix_leaves_dev: bad shape");
+    if (n_rows == 0 || row_len == 0 || n_rows > pmx::kMaxLaunchUnits) return pmx::set_error(PMX_ERR_ARG, "pmx_test_matrix_leaves_dev: bad shape");
     if (!pmx::aligned16(d_matrix) || !pmx::aligned16(d_leaves)) return pmx::set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned");
     PMX_BIND(ctx);
     PMX_HIP(pmx::launch_hash_strided(ctx->dev, ctx->t, d_matrix, row_len, row_stride, elem_stride, d_leaves, 1, n_rows, (hipStream_t)stream));

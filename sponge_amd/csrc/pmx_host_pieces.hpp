@@ -1,4 +1,4 @@
-// How the host-buffer sponge entries (pmx_api.cpp: resident_walk behind sponge_host and squeeze_cut_host; varlen_host) cut a call that is longer than one device
+// How the host-buffer sponge entries (pmx_sponge.cpp: resident_walk behind sponge_host and squeeze_cut_host; varlen_host) cut a call that is longer than one device
 // call may be.  The pass drivers launch one kernel per permutation a sponge of the call can need, and a device call is limited to
 // kMaxPasses of them: kMaxPasses rates of elements per sponge.  The reference takes any length (src/poseidon/mod.rs:232-254, 321-341),
 // so the host entries walk a longer call in pieces, the sponges resident on the device in between.

@@ -34,12 +34,31 @@ hipError_t launch_grind(const DevConfig &c, uint32_t t, const uint64_t *base, ui
                         uint64_t *best, hipStream_t st);
 // Device scratch for the pass lists of the drivers that run as passes (pmx_engine_launch.hpp: sponge_passes): `get` hands out at least
 // `bytes` bytes that stay valid for everything enqueued on `st` by this call, `done` is called once behind the call's last launch
-// (pmx_api.cpp: a pool of blocks owned by the context, each released by an event recorded there).  Engines that need no lists
+// (pmx_sponge.cpp: a pool of blocks owned by the context, each released by an event recorded there).  Engines that need no lists
 // call neither.
 struct PassScratch {
     void *owner = nullptr;
     hipError_t (*get)(void *owner, hipStream_t st, size_t bytes, uint32_t **out) = nullptr;
     void (*done)(void *owner, hipStream_t st, uint32_t *block) = nullptr;
+};
+// One block of a PassScratch for the length of a scope: `take` is the `get`, and the scope's end - whichever way out, behind everything
+// the scope enqueued on `st` - is the `done` of a block that was taken.  A block that is not given back is never handed out again.
+class PassLease {
+public:
+    PassLease(const PassScratch &from, hipStream_t st) : from_(from), st_(st) {}
+    ~PassLease() {
+        if (block && err == hipSuccess && from_.done) from_.done(from_.owner, st_, block);
+    }
+    PassLease(const PassLease &) = delete;
+    PassLease &operator=(const PassLease &) = delete;
+    hipError_t take(size_t bytes) { return err = from_.get(from_.owner, st_, bytes, &block); }
+
+    uint32_t *block = nullptr;      // what `take` got; null before it and after one that failed
+    hipError_t err = hipSuccess;    // of the take
+
+private:
+    const PassScratch &from_;
+    hipStream_t st_;
 };
 hipError_t launch_absorb(const DevConfig &c, uint32_t t, uint64_t *states, uint32_t *tag, uint32_t *index,
                          const uint64_t *in, size_t in_len, size_t n, hipStream_t st, const PassScratch &scratch);

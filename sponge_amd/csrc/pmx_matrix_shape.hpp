@@ -1,4 +1,4 @@
-// The index arithmetic of the matrix entries (pmx_matrix_*, pmx_api.cpp): how a layout addresses its elements, how the rows of a matrix
+// The index arithmetic of the matrix entries (pmx_matrix_*, pmx_matrix.cpp): how a layout addresses its elements, how the rows of a matrix
 // are cut into slabs for the upload, the byte sizes, and the 2-D copy that lifts a slab of rows out of a column-major matrix.
 // Pure 64-bit arithmetic, host only; compiled into tests/matrix/matrix_host.cpp as well.
 //

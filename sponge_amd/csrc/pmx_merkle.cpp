@@ -137,7 +137,7 @@ int paths_dev(pmx_ctx *ctx, const uint64_t *d_nodes, size_t n_leaves, uint32_t a
     if (int rc = arity_fits(ctx, arity)) return rc;
     if (k == 0 || depth == 0) return PMX_OK;
     const size_t per = depth * (arity - 1);     // elements per path (depth <= 64, arity <= PMX_MAX_WIDTH)
-    if (k > (SIZE_MAX / 32) / per || k > ((size_t)0x7fffffff * 64) / per) return set_error(PMX_ERR_ARG, "batch too large");
+    if (k > (SIZE_MAX / 32) / per || k > kMaxLaunchUnits / per) return set_error(PMX_ERR_ARG, "batch too large");
     if (!aligned16(d_nodes) || !aligned16(d_paths)) return misaligned();
     PMX_BIND(ctx);
     PMX_HIP((ragged ? launch_paths_gather_ragged : launch_paths_gather)(d_nodes, n_leaves, arity, depth, d_indices, d_paths, k, (hipStream_t)stream));
@@ -155,7 +155,7 @@ int verify_dev(pmx_ctx *ctx, const uint64_t *d_leaves, const uint64_t *d_indices
     if (int rc = arity_fits(ctx, arity)) return rc;
     if (k == 0) return PMX_OK;
     // (depth <= 64 and arity <= PMX_MAX_WIDTH here: the products below stay small)
-    if (k > ((size_t)0x7fffffff * 64) / (pairs ? 1 : arity) || k > (SIZE_MAX / 32) / (arity + 1) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
+    if (k > kMaxLaunchUnits / (pairs ? 1 : arity) || k > (SIZE_MAX / 32) / (arity + 1) || (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
         return set_error(PMX_ERR_ARG, "batch too large");
     if (!aligned16(d_leaves) || !aligned16(d_paths) || !aligned16(d_work) || !aligned16(d_root)) return misaligned();
     PMX_BIND(ctx);
@@ -184,7 +184,7 @@ int update_dev(pmx_ctx *ctx, uint64_t *d_nodes, size_t n_leaves, uint32_t arity,
     if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
     if (int rc = arity_fits(ctx, arity)) return rc;
     if (k == 0) return PMX_OK;
-    if (k > ((size_t)0x7fffffff * 64) / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
+    if (k > kMaxLaunchUnits / arity || k > (SIZE_MAX / 32) / (arity + 1)) return set_error(PMX_ERR_ARG, "batch too large");
     PMX_BIND(ctx);
     hipStream_t st = (hipStream_t)stream;
     uint64_t *cur = d_work, *rows = d_work + k * 4;

@@ -1,6 +1,6 @@
 // Host-side preparation of a validated config for the kernels: modulus view, conversion constants and the
 // round constants / MDS matrix rewritten into the internal field form (29-bit limbs, x * 2^261 mod p).
-// Shared by pmx_api.cpp (which uploads the table) and the CPU-side algorithm check in tests/hostcheck.
+// Shared by pmx_context.cpp (which uploads the table) and the CPU-side algorithm check in tests/hostcheck.
 // The schedules themselves are derived in pmx_derive.hpp; this file lays them out: the serialisers, the table writer and prepare().
 #pragma once
 #include <cstring>

@@ -14,13 +14,16 @@ CSRC = os.path.join(ROOT, "sponge_amd", "csrc")
 
 WINDOW = {"pmx_device_window_%d" % n for n in range(1, 9)}
 DEVICE = WINDOW | {"pmx_device", "pmx_tree_moves", "pmx_convert", "pmx_diag"}
-HOST = {"pmx_api", "pmx_merkle", "pmx_mgpu", "pmx_mgpu_test", "pmx_hooks", "pmx_hooks_test", "pmx_params"}
+API = {"pmx_context", "pmx_host_call", "pmx_batch", "pmx_sponge", "pmx_matrix"}
+HOST = API | {"pmx_merkle", "pmx_mgpu", "pmx_mgpu_test", "pmx_hooks", "pmx_hooks_test", "pmx_params"}
 
 # header -> (objects that must be rebuilt, objects that must not be)
 CASES = {
-    "pmx_ctx.hpp": ({"pmx_api"}, DEVICE),
-    "pmx_staging.hpp": ({"pmx_api"}, DEVICE),
-    "pmx_prepare.hpp": ({"pmx_api"}, DEVICE),
+    "pmx_ctx.hpp": (API, DEVICE),
+    "pmx_staging.hpp": (API, DEVICE),
+    "pmx_prepare.hpp": ({"pmx_context"}, DEVICE | {"pmx_batch", "pmx_sponge", "pmx_matrix", "pmx_merkle"}),
+    "pmx_matrix_shape.hpp": ({"pmx_matrix"}, {"pmx_sponge", "pmx_batch", "pmx_context"}),
+    "pmx_grind_plan.hpp": ({"pmx_sponge"}, {"pmx_matrix", "pmx_batch", "pmx_context"}),
     "pmx_field.hpp": (WINDOW | {"pmx_device", "pmx_convert"}, set()),
     "pmx_engines.hpp": (WINDOW | {"pmx_device"}, HOST | {"pmx_tree_moves"}),
 }

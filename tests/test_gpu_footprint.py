@@ -529,7 +529,7 @@ N_ONCE = 65
 
 
 def _laid_out(entry, label, seed=77):
-    """a valid call of N_ONCE units in an arena: (arena, shape, buffers pmx_api.cpp checks with aligned16)"""
+    """a valid call of N_ONCE units in an arena: (arena, shape, buffers pmx_host_call.cpp checks with aligned16)"""
     f, cfg, cr = _config(label)
     t, r, n = cfg.t, cfg.rate, N_ONCE
     st, tag, idx = _sponges(f, t, r, n, seed)

@@ -247,7 +247,7 @@ def varlen_cases(b, n, seed=47):
 
 
 def packed_limit(t, length):
-    """the largest n whose packed [states | io | tag | index] image is at most kSmallCallBytes (sponge_host, pmx_api.cpp)"""
+    """the largest n whose packed [states | io | tag | index] image is at most kSmallCallBytes (sponge_host, pmx_sponge.cpp)"""
     def packed(n):
         return n * t * 32 + n * length * 32 + 2 * ((n * 4 + 15) // 16 * 16)
     last = max(n for n in range(1, 4096) if packed(n) <= SMALL)

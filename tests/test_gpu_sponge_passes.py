@@ -195,7 +195,7 @@ def test_a_call_longer_than_65536_rates_is_refused_not_launched():
 def test_host_calls_longer_than_65536_rates_are_cut_into_pieces_the_reference_takes_any_length():
     """The reference's absorb / squeeze take any length (src/poseidon/mod.rs:232-254, 321-341) and the drop-in type passes a whole
     input as one call with n = 1; the device call is limited to 65536 rates, so the host-buffer entry points cut a longer call into
-    pieces (pmx_api.cpp: sponge_host).  t = 3 (rate 2, the reference's default shape): absorb(65536 * 2 + 1) on one sponge, then a
+    pieces (pmx_sponge.cpp: sponge_host).  t = 3 (rate 2, the reference's default shape): absorb(65536 * 2 + 1) on one sponge, then a
     squeeze whose LAST piece would be exactly one rate from a sponge standing inside its rate - the cut that would skip a permutation
     through the test of mod.rs:175 - and the same on three sponges in different modes (n > 1: the pieces are packed row by row)."""
     f, cfg, cr = _config("bls12_381_fr", None, 255, 2, 5, 8, 31)
@@ -230,7 +230,7 @@ def test_host_calls_longer_than_65536_rates_are_cut_into_pieces_the_reference_ta
 
 def test_host_calls_on_both_sides_of_the_packed_path_agree_with_the_c_oracle_and_each_other():
     """The host entries stage a call of at most 64 KiB - [states | io | tag | index], the mode words padded to 16 bytes - through the
-    context's page-locked block with one copy each way, and run every larger call as the resident walk (pmx_api.cpp: sponge_host,
+    context's page-locked block with one copy each way, and run every larger call as the resident walk (pmx_sponge.cpp: sponge_host,
     kSmallCallBytes).  t = 3, rate 2, mixed modes, absorb(4) then squeeze(3) through the host entries: 2100 sponges (far past the
     switch) and 500 (112 000 bytes for the absorb, 104 000 for the squeeze: past it too, though nearer), and the batch sizes on either
     side of the switch itself - absorb(4) packs up to 282 sponges (65 440 bytes; 283: 65 664), squeeze(3) up to 327 (65 408; 328:

@@ -1,5 +1,5 @@
 """How the host-buffer sponge entries cut a call that is longer than one device call may be (sponge_amd/csrc/pmx_host_pieces.hpp; the
-entries are sponge_host, squeeze_cut_host and varlen_host of pmx_api.cpp), on the CPU: the header compiled for the host behind
+entries are sponge_host, squeeze_cut_host and varlen_host of pmx_sponge.cpp), on the CPU: the header compiled for the host behind
 tests/host_pieces/pieces_host.cpp, with max_len shrunk to a few rates.
 - The cut of a fixed-length call: positive pieces of at most max_len that sum to the call, none but the first exactly one rate.
 - The same cut against the C oracle (oracle/cref: sponge_squeeze, sponge_absorb): piece by piece is one whole call - outputs, end state

@@ -2,7 +2,7 @@
 pmx_ctx.hpp hands a block out for one), on the CPU: the header compiled for the host behind tests/staging/staging_host.cpp.
 - Every section starts on a 16-byte boundary, and the offsets are the running aligned sums.
 - The overflow flag is set exactly when a product or the (aligned) sum exceeds SIZE_MAX.
-- Every layout the entries of pmx_api.cpp and pmx_merkle.cpp state comes out with the offsets their bodies computed by hand before
+- Every layout the entries of pmx_batch.cpp, pmx_sponge.cpp, pmx_matrix.cpp and pmx_merkle.cpp state comes out with the offsets their bodies computed by hand before
   the header existed: those expressions are written out here.
 - tests/staging/sanitize_main.cpp, a program of its own, walks blocks of exactly bytes() bytes under ASan + UBSan."""
 import ctypes

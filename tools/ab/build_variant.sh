@@ -23,5 +23,5 @@ for tu in 0 1 2 3 4; do
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC -shared -fPIC --offload-arch=gfx950 $B/pmx_device_0.o $B/pmx_device_1.o $B/pmx_device_2.o $B/pmx_device_3.o $B/pmx_device_4.o $C/build/pmx_device_window_[5-8].o $C/build/pmx_tree_moves.o $C/build/pmx_convert.o $C/build/pmx_api.o $C/build/pmx_merkle.o $C/build/pmx_mgpu.o $C/build/pmx_hooks.o $C/build/pmx_params.o -ldl -o $R/tools/ab/libposeidon_$NAME.so
+$HIPCC -shared -fPIC --offload-arch=gfx950 $B/pmx_device_0.o $B/pmx_device_1.o $B/pmx_device_2.o $B/pmx_device_3.o $B/pmx_device_4.o $C/build/pmx_device_window_[5-8].o $C/build/pmx_tree_moves.o $C/build/pmx_convert.o $C/build/pmx_context.o $C/build/pmx_host_call.o $C/build/pmx_batch.o $C/build/pmx_sponge.o $C/build/pmx_matrix.o $C/build/pmx_merkle.o $C/build/pmx_mgpu.o $C/build/pmx_hooks.o $C/build/pmx_params.o -ldl -o $R/tools/ab/libposeidon_$NAME.so
 ls -la $R/tools/ab/libposeidon_$NAME.so

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Wall time of the host-buffer sponge entries on pageable buffers (pmx_api.cpp: sponge_host, squeeze_cut_host, varlen_host), per
+"""Wall time of the host-buffer sponge entries on pageable buffers (pmx_sponge.cpp: sponge_host, squeeze_cut_host, varlen_host), per
 step, BLS12-381 Fr t = 3 (rate 2):
   packed n=1            one sponge, absorb(3) + squeeze(3): the page-locked block of a small call, one copy each way
   absorb(8) / squeeze(3) / squeeze_bytes(32) / absorb_varlen(0..8)     2^16 sponges: the resident walk with one piece

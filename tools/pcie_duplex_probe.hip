@@ -1,5 +1,5 @@
 // What the link gives a round trip of 96 MiB each way (2^20 t = 3 states): SDMA copies and kernels that read / write a page-locked host
-// buffer themselves, alone and in pairs.  The host path's pipeline (pmx_api.cpp: host_pipeline) is priced against the best pair.
+// buffer themselves, alone and in pairs.  The host path's pipeline (pmx_batch.cpp: host_pipeline) is priced against the best pair.
 //   hipcc -O2 --offload-arch=gfx950 tools/pcie_duplex_probe.hip -o tools/pcie_duplex_probe
 #include <hip/hip_runtime.h>
 #include <chrono>
