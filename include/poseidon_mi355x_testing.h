@@ -56,6 +56,23 @@ int pmx_test_merkle_fixed_piece(uint64_t leaves);
 int pmx_test_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
                                uint64_t *d_leaves, void *stream);
 
+/* Injected HIP failures.  Every checked HIP call of the single-device entries (contexts, the host-buffer entries, the pass-scratch pool;
+ * not the device groups, not the benchmark diagnostics) asks one function first.  The test build counts those calls per THREAD
+ * (the state is thread_local, unlike the hooks above) and answers the armed one with hipErrorOutOfMemory in place of making it: the entry
+ * leaves at once through its ordinary error path, PMX_ERR_HIP with "injected" and the call's expression text in pmx_last_error().  A
+ * launcher of the kernel files is failed as a whole, through the checked call that wraps it.  Nothing reaches the device.
+ * pmx_test_fail_hip: the calling thread's nth checked call from now fails (1-based), once; 0 disarms.  Either way the count starts again.
+ * pmx_test_hip_calls: the checked calls of this thread since the last pmx_test_fail_hip.
+ * pmx_test_hip_fired: the text "injected in place of <expression>" of the failure made since the last pmx_test_fail_hip, "" if none was:
+ *   how a test finds a call whose failure the product absorbs (a registration that falls back, the event of a pool block). */
+int pmx_test_fail_hip(int64_t nth);
+int64_t pmx_test_hip_calls(void);
+const char *pmx_test_hip_fired(void);
+
+/* The pass-scratch pool of a context, read under its lock: the blocks it holds, those held by a call (taken and not given back - 0 between
+ * calls, whichever way the last one ended) and those whose event could not be recorded, which no other stream is handed again. */
+int pmx_test_pass_pool(pmx_ctx *ctx, size_t *blocks, size_t *held, size_t *poisoned);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,10 @@ TEST_HOOK_SIGNATURES = {
     "pmx_test_matrix_slab_rows": (ctypes.c_int, [ctypes.c_uint64]),
     "pmx_test_merkle_fixed_piece": (ctypes.c_int, [ctypes.c_uint64]),
     "pmx_test_matrix_leaves_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _sz, _sz, _u64p, ctypes.c_void_p]),
+    "pmx_test_fail_hip": (ctypes.c_int, [ctypes.c_int64]),
+    "pmx_test_hip_calls": (ctypes.c_int64, []),
+    "pmx_test_hip_fired": (ctypes.c_char_p, []),
+    "pmx_test_pass_pool": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
 }
 
 _lib = None

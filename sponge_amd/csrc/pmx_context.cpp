@@ -31,6 +31,9 @@ int set_error(int code, const char *fmt, ...) {
 }
 
 int hip_fail(hipError_t e, const char *what) {
+    // (a failure the test build made says so and names the call that was not made - it may lie below `what`, in the pass-scratch pool;
+    // the wording is pmx_hooks.cpp's, the shipped library has none of it)
+    if (const char *note = hip_injected()) return set_error(PMX_ERR_HIP, "%s: %s [%s]", what, hipGetErrorString(e), note);
     return set_error(PMX_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
@@ -96,14 +99,14 @@ extern "C" int pmx_ctx_create(const pmx_config *cfg, int device, pmx_ctx **out) 
     if (guard.err != hipSuccess) { delete ctx; return hip_fail(guard.err, "hipSetDevice"); }
 
     const size_t bytes = pp.consts.size() * 4;
-    e = hipMalloc((void **)&ctx->d_consts, bytes);
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_consts, pp.consts.data(), bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking);
+    e = PMX_HIP_CALL(hipMalloc((void **)&ctx->d_consts, bytes));
+    if (e == hipSuccess) e = PMX_HIP_CALL(hipMemcpy(ctx->d_consts, pp.consts.data(), bytes, hipMemcpyHostToDevice));
+    if (e == hipSuccess) e = PMX_HIP_CALL(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    if (e == hipSuccess) e = PMX_HIP_CALL(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    if (e == hipSuccess) e = PMX_HIP_CALL(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
     for (int i = 0; i < pmx_ctx::kPipeChunks && e == hipSuccess; ++i) {
-        e = hipEventCreateWithFlags(&ctx->pipe_up[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->pipe_done[i], hipEventDisableTiming);
+        e = PMX_HIP_CALL(hipEventCreateWithFlags(&ctx->pipe_up[i], hipEventDisableTiming));
+        if (e == hipSuccess) e = PMX_HIP_CALL(hipEventCreateWithFlags(&ctx->pipe_done[i], hipEventDisableTiming));
     }
     if (e != hipSuccess) {
         (void)ctx_free(ctx);   // (`e` is the first failure: whatever the teardown meets does not reach the text)

@@ -49,9 +49,21 @@ namespace pmx {
 
 int hip_fail(hipError_t e, const char *what);
 
+// The one door every checked HIP call of the single-device entries goes through, in front of the call (`what`: its expression text).
+// Defined in pmx_hooks.cpp like grind_chunk() below: in the shipped library it returns hipSuccess and holds no state; the test build
+// counts the calling thread's checked calls and, when pmx_test_fail_hip (include/poseidon_mi355x_testing.h) armed one, answers
+// hipErrorOutOfMemory in its place - the call itself is then NOT made, and the entry leaves through its ordinary error path.
+hipError_t hip_inject(const char *what);
+// The wording of the calling thread's injected failure, once: hip_fail asks it for the message, and so does a site that absorbs the
+// failure of its call, so that it cannot word a later one.  Null otherwise, and always in the shipped library.
+const char *hip_injected();
+
+// a checked call as an expression, for the sites that look at the status themselves
+#define PMX_HIP_CALL(expr) (::pmx::hip_inject(#expr) == hipSuccess ? (expr) : hipErrorOutOfMemory)
+
 #define PMX_HIP(expr)                                             \
     do {                                                          \
-        hipError_t e_ = (expr);                                   \
+        hipError_t e_ = PMX_HIP_CALL(expr);                       \
         if (e_ != hipSuccess) return ::pmx::hip_fail(e_, #expr);  \
     } while (0)
 
@@ -138,6 +150,12 @@ public:
     // limit, a range that is not plain memory) leaves the buffer as it is: false.  An empty buffer holds nothing back.  A caller whose
     // path does not hang on the answer says so: a buffer too small to register is then not even asked about.
     bool pin(const void *p, size_t bytes, bool answer_wanted = true);
+    // `bytes` of host memory that live until the streams are drained: where an inout buffer of the caller comes down, to be copied into
+    // the caller's memory only once the call can no longer fail.  One per call; std::bad_alloc is the entry's catch-all's.
+    char *landing(size_t bytes) {
+        landing_.resize(bytes);
+        return landing_.data();
+    }
 
     pmx_ctx *const ctx;
 
@@ -145,6 +163,7 @@ private:
     DeviceGuard guard_;
     std::lock_guard<std::mutex> lock_;
     ScopedPin pins_[2];
+    std::vector<char> landing_;   // (freed behind the drain: downloads may be in flight into it)
     StreamDrain drain_;
     int slots_ = 0, pinned_ = 0;
 };

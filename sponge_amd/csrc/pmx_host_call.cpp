@@ -58,8 +58,9 @@ bool HostCall::pin(const void *p, size_t bytes, bool answer_wanted) {
     if (!answer_wanted && bytes < ScopedPin::kMinBytes) return false;
     if (is_pinned(p)) return true;
     if (bytes < ScopedPin::kMinBytes || pinned_ == 2) return false;
-    if (hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) != hipSuccess) {
+    if (PMX_HIP_CALL(hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault)) != hipSuccess) {
         (void)hipGetLastError();
+        (void)hip_injected();   // (absorbed: pmx_ctx.hpp)
         return false;
     }
     pins_[pinned_++].ptr = const_cast<void *>(p);

@@ -55,9 +55,9 @@ static hipError_t ctx_pass_scratch(void *owner, hipStream_t st, size_t bytes, ui
         size_t want = (bytes + 4095) & ~(size_t)4095;
         for (const pmx_ctx::PassBlock &b : ctx->pass_pool)  // grow in doublings: an outgrown block stays in the pool for smaller calls
             if (b.bytes * 2 > want && b.bytes < bytes) want = b.bytes * 2;
-        hipError_t e = hipMalloc(&fresh.ptr, want);
+        hipError_t e = PMX_HIP_CALL(hipMalloc(&fresh.ptr, want));
         if (e != hipSuccess) return e;
-        e = hipEventCreateWithFlags(&fresh.done, hipEventDisableTiming);
+        e = PMX_HIP_CALL(hipEventCreateWithFlags(&fresh.done, hipEventDisableTiming));
         if (e != hipSuccess) {
             (void)hipFree(fresh.ptr);
             return e;
@@ -77,8 +77,9 @@ static void ctx_pass_done(void *owner, hipStream_t st, uint32_t *block) {
         if (b.ptr != block) continue;
         // a record that failed leaves `done` unrecorded (or holding an older, completed record): a query would call the block idle while
         // this call's launches may still read it - such a block is never handed to another stream again (its own stream orders the reuse)
-        if (hipEventRecord(b.done, st) != hipSuccess) {
+        if (PMX_HIP_CALL(hipEventRecord(b.done, st)) != hipSuccess) {
             (void)hipGetLastError();
+            (void)hip_injected();   // (absorbed: pmx_ctx.hpp)
             b.poisoned = true;
         }
         b.recorded = true;
@@ -126,8 +127,9 @@ static int check_modes(const pmx_ctx *ctx, const uint32_t *tag, const uint32_t *
 }
 
 // n sponges resident on the device for the length of a host-buffer call: [states | io | tag | index] in one staging block, where `io`
-// is the data of a packed call (sponge_host) and empty otherwise.  The caller reads nothing back before its last piece is enqueued: a
-// call that fails half way leaves the caller's sponges as they were.  (st_bytes: the caller's batch_bytes(n, t).)
+// is the data of a packed call (sponge_host) and empty otherwise.  Nothing comes back into the caller's states and mode words before the
+// call's last checked HIP call has succeeded (download / deliver): a call that fails - half way, or in its last synchronise - leaves the
+// caller's sponges as they were.  (st_bytes: the caller's batch_bytes(n, t).)
 struct ResidentSponges {
     Staging layout;
     size_t n, st_bytes, o_io, o_tag, o_index;
@@ -155,12 +157,20 @@ struct ResidentSponges {
         PMX_HIP(hipMemsetAsync(d, 0, layout.bytes(), st));
         return PMX_OK;
     }
-    int download(uint64_t *h_states, uint32_t *h_tag, uint32_t *h_index, hipStream_t st) const {
-        PMX_HIP(hipMemcpyAsync(h_states, states(), st_bytes, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(h_tag, tag(), n * 4, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(h_index, index(), n * 4, hipMemcpyDeviceToHost, st));
+    // The way back is two steps, so that no failure can leave the caller with states of one call and mode words of another: the whole block
+    // down into the call's landing memory and the stream synchronised, which can fail; then host copies into the caller's arrays, which cannot.
+    int download(HostCall &call, hipStream_t st) {
+        h = call.landing(layout.bytes());
+        PMX_HIP(hipMemcpyAsync(h, d, layout.bytes(), hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipStreamSynchronize(st));
         return PMX_OK;
     }
+    void deliver(uint64_t *h_states, uint32_t *h_tag, uint32_t *h_index) const {
+        std::memcpy(h_states, h, st_bytes);
+        std::memcpy(h_tag, h + o_tag, n * 4);
+        std::memcpy(h_index, h + o_index, n * 4);
+    }
+    char *h = nullptr;   // the landing memory of `download`
 };
 
 // `width` bytes of each of n rows between the caller's rows (of its pitch) and a packed [n][width] device block: a piece's columns.
@@ -199,8 +209,8 @@ static int resident_walk(HostCall &call, uint64_t *states, uint32_t *tag, uint32
         if (down && (rc = copy_columns(down + col, row, d_io, width, width, n, hipMemcpyDeviceToHost, st))) return rc;
         done += piece;
     } while (done < elems);
-    if ((rc = sp.download(states, tag, index, st))) return rc;
-    PMX_HIP(hipStreamSynchronize(st));
+    if ((rc = sp.download(call, st))) return rc;
+    sp.deliver(states, tag, index);
     return PMX_OK;
 }
 
@@ -485,10 +495,11 @@ static int varlen_host(pmx_ctx *ctx, uint64_t *states, uint32_t *tag, uint32_t *
     if (hash) {
         if ((rc = pmx_sponge_squeeze_batch_dev(ctx, sp.states(), sp.tag(), sp.index(), (uint64_t *)d_out, out_len, n, st))) return rc;
         PMX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    } else if ((rc = sp.download(states, tag, index, st))) {
-        return rc;
+        PMX_HIP(hipStreamSynchronize(st));
+        return PMX_OK;
     }
-    PMX_HIP(hipStreamSynchronize(st));
+    if ((rc = sp.download(call, st))) return rc;
+    sp.deliver(states, tag, index);
     return PMX_OK;
     PMX_ABI_END
 }

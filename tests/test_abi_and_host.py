@@ -47,8 +47,10 @@ def test_library_exports_every_declared_symbol():
     for name in hooks:
         assert not hasattr(lib, name), f"{name}: a test hook is exported by the shipped library"
     blob = open(_lib.LIB_PATH, "rb").read()
-    for needle in (b"PMX_RCCL_LIBRARY", b"pmx_mgpu_test_", b"pmx_test_hooks_enabled", b"injected failure"):
+    for needle in (b"PMX_RCCL_LIBRARY", b"pmx_mgpu_test_", b"pmx_test_hooks_enabled", b"injected failure",
+                   b"pmx_test_fail_hip", b"pmx_test_hip_calls", b"pmx_test_hip_fired", b"pmx_test_pass_pool", b"injected in place"):
         assert needle not in blob, needle
+    assert {"pmx_test_fail_hip", "pmx_test_hip_calls", "pmx_test_hip_fired", "pmx_test_pass_pool"} <= set(hooks)
 
 
 def test_the_test_library_is_the_shipped_abi_plus_the_hooks():
