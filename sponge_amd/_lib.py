@@ -202,6 +202,18 @@ SIGNATURES = {
     "pmx_mgpu_merkle_2to1": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _u64p]),
 }
 
+# include/poseidon_mi355x_resident.h: the device-resident forms of families whose main-header entries take host buffers; exported by the
+# shipped library and the test library, bound next to SIGNATURES
+RESIDENT_SIGNATURES = {
+    "pmx_matrix_view_extent": (ctypes.c_int, [_sz, _sz, _sz, _sz, ctypes.POINTER(_sz)]),
+    "pmx_matrix_leaves_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _sz, _sz, _u64p, ctypes.c_void_p]),
+    "pmx_matrix_commit_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _sz, _sz, ctypes.c_uint32, _u64p, ctypes.c_void_p]),
+    "pmx_matrix_open_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _sz, _sz, _sz, _u64p, ctypes.c_uint32, _u64p, _sz, _u64p, _u64p,
+                                           ctypes.c_void_p]),
+    "pmx_matrix_verify_rows_dev": (ctypes.c_int, [ctypes.c_void_p, _u64p, _sz, _u64p, _u64p, _sz, ctypes.c_uint32, _sz, _sz, _u64p,
+                                                  ctypes.c_void_p, _u64p, ctypes.c_void_p]),
+}
+
 # include/poseidon_mi355x_diag.h: libposeidon_mi355x_diag.so, the benchmark diagnostics (bench.py) - not part of the shipped library
 DIAG_LIB_PATH = os.path.join(HERE, "libposeidon_mi355x_diag.so")
 DIAG_SIGNATURES = {
@@ -263,7 +275,7 @@ def lib() -> ctypes.CDLL:
                 f"{_path} is missing: build it with `make -C sponge_amd/csrc` "
                 "(or __graft_entry__.build()). There is no CPU fallback.")
         handle = ctypes.CDLL(_path)
-        sigs = list(SIGNATURES.items()) + (list(TEST_HOOK_SIGNATURES.items()) if _hooks else [])
+        sigs = list(SIGNATURES.items()) + list(RESIDENT_SIGNATURES.items()) + (list(TEST_HOOK_SIGNATURES.items()) if _hooks else [])
         for name, (restype, argtypes) in sigs:
             if _older and not hasattr(handle, name):
                 continue

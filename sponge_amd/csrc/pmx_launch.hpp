@@ -136,6 +136,11 @@ hipError_t launch_paths_gather_ragged(const uint64_t *nodes, size_t n_leaves, ui
                                       uint64_t *paths, size_t k, hipStream_t st);
 hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first,
                                         uint64_t width, uint32_t arity, uint64_t *rows, size_t k, hipStream_t st);
+// Opened rows of a matrix on the device (pmx_matrix_open_dev): rows[i][j] = element (indices[i], j) of the strided view - the 4 words at
+// matrix + (indices[i] * row_stride + j * elem_stride) * 4 - for j < row_len, rows [k][row_len][4] with each row contiguous; an all-zero
+// row for an index >= n_rows, and nothing outside the view is read.  k * row_len <= kMaxLaunchUnits, k >= 1.
+hipError_t launch_matrix_rows(const uint64_t *matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
+                              const uint64_t *indices, uint64_t *rows, size_t k, hipStream_t st);
 // Fixed-depth trees (pmx_merkle_fixed*, pmx_merkle_frontier_append): elems[list[2 i]] = elems[list[2 i + 1]] for i < k, elements of 4 words
 // of one device array, the pairs built by the host (pmx_merkle_frontier.hpp); no destination is a source of the same launch.  k >= 1.
 hipError_t launch_node_place(uint64_t *elems, const uint64_t *list, size_t k, hipStream_t st);

@@ -1,10 +1,13 @@
-// C ABI of libposeidon_mi355x.so: the matrix commitment - row digests, the tree over them, opened rows and their verification.
+// C ABI of libposeidon_mi355x.so: the matrix commitment - row digests, the tree over them, opened rows and their verification - on a
+// matrix in host memory (include/poseidon_mi355x.h) and, at the end of the file, on one that lives on the device
+// (include/poseidon_mi355x_resident.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 
 #include "../../include/poseidon_mi355x.h"
+#include "../../include/poseidon_mi355x_resident.h"
 #include "pmx_ctx.hpp"
 #include "pmx_internal.hpp"
 #include "pmx_launch.hpp"
@@ -169,4 +172,116 @@ extern "C" int pmx_matrix_verify_rows(pmx_ctx *ctx, const uint64_t *rows, size_t
     if (k > kMaxLaunchUnits / arity) return set_error(PMX_ERR_ARG, "batch byte size overflows size_t");
     return verify_host(ctx, nullptr, rows, row_len, indices, paths, depth, arity, (uint64_t)n_rows, false, k, root, ok_out);
     PMX_ABI_END
+}
+
+// ---- the device-resident forms (include/poseidon_mi355x_resident.h) --------------------------------------------------------------------
+// The matrix is a strided view of the caller's device memory (pmx_matrix_shape.hpp: matrix_view_extent), read where it lies by the
+// kernel the slabs above are hashed with; the tree, the path gather and the climb are the ragged entries' own (pmx_merkle.cpp), called
+// through their *_dev entry points on the caller's stream.  Each entry tests everything those would refuse before its first launch, so
+// a refused call has launched nothing.  Enqueue only: nothing is allocated, nothing synchronised, and every entry may be captured.
+namespace {
+
+int matrix_view_args(size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride, const char *who, uint64_t *extent) {
+    if (n_rows == 0) return set_error(PMX_ERR_ARG, "%s: a matrix needs at least one row", who);
+    if (row_len == 0) return set_error(PMX_ERR_ARG, "%s: a row needs at least one element", who);
+    if (row_stride == 0 || elem_stride == 0) return set_error(PMX_ERR_ARG, "%s: a stride of a view must be at least one element", who);
+    if (!matrix_view_extent(n_rows, row_len, row_stride, elem_stride, extent) || *extent > SIZE_MAX / kMatrixElemBytes)
+        return set_error(PMX_ERR_ARG, "%s: the view's byte size overflows size_t", who);
+    return PMX_OK;
+}
+// a view some launch reads n_rows rows of
+int matrix_view_launch_args(size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride, const char *who) {
+    uint64_t extent = 0;
+    if (int rc = matrix_view_args(n_rows, row_len, row_stride, elem_stride, who, &extent)) return rc;
+    if (n_rows > kMaxLaunchUnits) return set_error(PMX_ERR_ARG, "batch too large");
+    return PMX_OK;
+}
+int matrix_misaligned() { return set_error(PMX_ERR_ARG, "device pointers must be 16-byte aligned"); }
+int matrix_indices_aligned(const uint64_t *d_indices) {
+    if ((uintptr_t)d_indices & 7u) return set_error(PMX_ERR_ARG, "d_indices must be 8-byte aligned");
+    return PMX_OK;
+}
+
+}  // namespace
+
+extern "C" int pmx_matrix_view_extent(size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride, size_t *extent_elems) {
+    if (!extent_elems) return set_error(PMX_ERR_ARG, "pmx_matrix_view_extent: null pointer");
+    uint64_t extent = 0;
+    if (int rc = matrix_view_args(n_rows, row_len, row_stride, elem_stride, "pmx_matrix_view_extent", &extent)) return rc;
+    *extent_elems = (size_t)extent;
+    return PMX_OK;
+}
+
+extern "C" int pmx_matrix_leaves_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride,
+                                     size_t elem_stride, uint64_t *d_leaves, void *stream) {
+    if (!ctx || !d_matrix || !d_leaves) return set_error(PMX_ERR_ARG, "pmx_matrix_leaves_dev: null pointer");
+    if (int rc = matrix_view_launch_args(n_rows, row_len, row_stride, elem_stride, "pmx_matrix_leaves_dev")) return rc;
+    if (!aligned16(d_matrix) || !aligned16(d_leaves)) return matrix_misaligned();
+    PMX_BIND(ctx);
+    PMX_HIP(launch_hash_strided(ctx->dev, ctx->t, d_matrix, row_len, row_stride, elem_stride, d_leaves, 1, n_rows, (hipStream_t)stream));
+    return PMX_OK;
+}
+
+extern "C" int pmx_matrix_commit_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride,
+                                     size_t elem_stride, uint32_t arity, uint64_t *d_nodes, void *stream) {
+    if (!ctx || !d_matrix || !d_nodes) return set_error(PMX_ERR_ARG, "pmx_matrix_commit_dev: null pointer");
+    if (int rc = matrix_view_launch_args(n_rows, row_len, row_stride, elem_stride, "pmx_matrix_commit_dev")) return rc;
+    size_t depth = 0, n_nodes = 0;
+    if (int rc = pmx_merkle_ragged_shape(n_rows, arity, &depth, &n_nodes)) return rc;
+    if (int rc = matrix_arity_fits(ctx, arity)) return rc;
+    if (!aligned16(d_matrix) || !aligned16(d_nodes)) return matrix_misaligned();
+    PMX_BIND(ctx);
+    PMX_HIP(launch_hash_strided(ctx->dev, ctx->t, d_matrix, row_len, row_stride, elem_stride, d_nodes, 1, n_rows, (hipStream_t)stream));
+    if (depth == 0) return PMX_OK;   // one row: its digest is the root
+    return pmx_merkle_ragged_dev(ctx, d_nodes, n_rows, arity, stream);
+}
+
+// the paths first (their entry tests its own arguments again), the rows behind them
+extern "C" int pmx_matrix_open_dev(pmx_ctx *ctx, const uint64_t *d_matrix, size_t n_rows, size_t row_len, size_t row_stride,
+                                   size_t elem_stride, const uint64_t *d_nodes, uint32_t arity, const uint64_t *d_indices, size_t k,
+                                   uint64_t *d_rows, uint64_t *d_paths, void *stream) {
+    if (!ctx || !d_matrix || ((!d_indices || !d_rows) && k)) return set_error(PMX_ERR_ARG, "pmx_matrix_open_dev: null pointer");
+    if (int rc = matrix_view_launch_args(n_rows, row_len, row_stride, elem_stride, "pmx_matrix_open_dev")) return rc;
+    if (d_paths && !d_nodes) return set_error(PMX_ERR_ARG, "pmx_matrix_open_dev: d_paths without d_nodes");
+    size_t depth = 0, n_nodes = 0;
+    if (d_nodes) {
+        if (int rc = pmx_merkle_ragged_shape(n_rows, arity, &depth, &n_nodes)) return rc;
+        if (int rc = matrix_arity_fits(ctx, arity)) return rc;
+        if (!d_paths && k && depth) return set_error(PMX_ERR_ARG, "pmx_matrix_open_dev: d_nodes without d_paths");
+    }
+    if (k == 0) return PMX_OK;
+    // (depth <= 64 and arity <= the rate here: the products stay small)
+    const size_t per = depth * (d_nodes ? arity - 1 : 0);     // elements per path
+    if (k > kMaxLaunchUnits / row_len || (d_nodes && k > kMaxLaunchUnits / arity) || (per && k > kMaxLaunchUnits / per))
+        return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_matrix) || !aligned16(d_rows) || !aligned16(d_nodes) || !aligned16(d_paths)) return matrix_misaligned();
+    if (int rc = matrix_indices_aligned(d_indices)) return rc;
+    PMX_BIND(ctx);
+    if (per)
+        if (int rc = pmx_merkle_ragged_paths_dev(ctx, d_nodes, n_rows, arity, d_indices, k, d_paths, stream)) return rc;
+    PMX_HIP(launch_matrix_rows(d_matrix, n_rows, row_len, row_stride, elem_stride, d_indices, d_rows, k, (hipStream_t)stream));
+    return PMX_OK;
+}
+
+extern "C" int pmx_matrix_verify_rows_dev(pmx_ctx *ctx, const uint64_t *d_rows, size_t row_len, const uint64_t *d_indices,
+                                          const uint64_t *d_paths, size_t depth, uint32_t arity, size_t n_rows, size_t k,
+                                          const uint64_t *d_root, uint8_t *d_ok, uint64_t *d_work, void *stream) {
+    if (!ctx || ((!d_rows || !d_indices || !d_ok || !d_work) && k) || (!d_paths && k && depth) || !d_root)
+        return set_error(PMX_ERR_ARG, "pmx_matrix_verify_rows_dev: null pointer");
+    if (row_len == 0) return set_error(PMX_ERR_ARG, "pmx_matrix_verify_rows_dev: a row needs at least one element");
+    size_t tree_depth = 0, n_nodes = 0;
+    if (int rc = pmx_merkle_ragged_shape(n_rows, arity, &tree_depth, &n_nodes)) return rc;
+    if (tree_depth != depth)
+        return set_error(PMX_ERR_ARG, "depth %zu is not the depth %zu of a tree of arity %u over %zu leaves", depth, tree_depth, arity, n_rows);
+    if (int rc = matrix_arity_fits(ctx, arity)) return rc;
+    if (k == 0) return PMX_OK;
+    // (the bounds of the climb, pmx_merkle.cpp: verify_dev, and the rows' own)
+    if (k > kMaxLaunchUnits / arity || k > (SIZE_MAX / 32) / (arity + 2) || k > (SIZE_MAX / 32) / row_len ||
+        (depth && k > (SIZE_MAX / 32) / (depth * (arity - 1))))
+        return set_error(PMX_ERR_ARG, "batch too large");
+    if (!aligned16(d_rows) || !aligned16(d_paths) || !aligned16(d_root) || !aligned16(d_work)) return matrix_misaligned();
+    if (int rc = matrix_indices_aligned(d_indices)) return rc;
+    PMX_BIND(ctx);
+    PMX_HIP(launch_hash_strided(ctx->dev, ctx->t, d_rows, row_len, row_len, 1, d_work, 1, k, (hipStream_t)stream));
+    return pmx_merkle_ragged_verify_paths_dev(ctx, d_work, d_indices, d_paths, depth, arity, n_rows, k, d_root, d_ok, d_work + k * 4, stream);
 }

@@ -1,5 +1,6 @@
 // The index arithmetic of the matrix entries (pmx_matrix_*, pmx_matrix.cpp): how a layout addresses its elements, how the rows of a matrix
-// are cut into slabs for the upload, the byte sizes, and the 2-D copy that lifts a slab of rows out of a column-major matrix.
+// are cut into slabs for the upload, the byte sizes, the 2-D copy that lifts a slab of rows out of a column-major matrix, and the span
+// of a strided view of a matrix on the device.
 // Pure 64-bit arithmetic, host only; compiled into tests/matrix/matrix_host.cpp as well.
 //
 // A matrix has n_rows rows of row_len elements of 32 bytes.  Row-major: element (i, j) at element index i * row_len + j.  Column-major:
@@ -39,6 +40,22 @@ inline bool matrix_bytes(uint64_t n_rows, uint64_t row_len, uint64_t *bytes) {
     *bytes = n_rows * row_len * kMatrixElemBytes;
     return true;
 }
+// A matrix that lives on the device is a strided view (include/poseidon_mi355x_resident.h): element (i, j) at element index
+// i * row_stride + j * elem_stride, whatever the strides - (1, ld) column-major, (row_len, 1) or (pitch, 1) row-major, a block of a
+// larger matrix.  The elements it spans, 1 + (n_rows - 1) * row_stride + (row_len - 1) * elem_stride: false for an empty dimension, a
+// zero stride, or a span whose byte size does not fit 64 bits.  Every element index of the view is then below *extent <= 2^59 - 1, so
+// the gather's 64-bit products cannot wrap.  Writes *extent only on success.
+inline bool matrix_view_extent(uint64_t n_rows, uint64_t row_len, uint64_t row_stride, uint64_t elem_stride, uint64_t *extent) {
+    if (n_rows == 0 || row_len == 0 || row_stride == 0 || elem_stride == 0) return false;
+    const uint64_t limit = UINT64_MAX / kMatrixElemBytes;   // the most elements whose bytes fit
+    if (n_rows > 1 && row_stride > limit / (n_rows - 1)) return false;
+    if (row_len > 1 && elem_stride > limit / (row_len - 1)) return false;
+    const uint64_t down = (n_rows - 1) * row_stride, across = (row_len - 1) * elem_stride;   // each <= limit < 2^59
+    if (down + across + 1 > limit) return false;
+    *extent = down + across + 1;
+    return true;
+}
+
 // the node array of the tree over the n_rows digests (pmx_merkle_shape.hpp: any leaf count): n_nodes and depth, refused as there
 inline MerkleShapeError matrix_tree_shape(uint64_t n_rows, uint32_t arity, MerkleShape *out) { return merkle_shape((size_t)n_rows, arity, false, out); }
 

@@ -1,5 +1,6 @@
 // The data movement of the Merkle entries (pmx_merkle.cpp) around the compression launches: authentication paths, node scatter / gather,
-// the placement lists of the fixed-depth trees, the chained rows of their sequential leaf updates.  The kernels move 16-byte pieces of
+// the placement lists of the fixed-depth trees, the chained rows of their sequential leaf updates - and the opened rows of a matrix
+// on the device (pmx_matrix.cpp).  The kernels move 16-byte pieces of
 // ABI elements and know nothing of a field or an engine, so - like pmx_convert.hip - this translation unit is compiled once.
 // Declarations: pmx_launch.hpp.
 #include <hip/hip_runtime.h>
@@ -139,6 +140,24 @@ __global__ void __launch_bounds__(256) node_children_bounded_kernel(const uint4 
     rows[gid] = v;
 }
 
+// ---- opened rows of a matrix on the device (pmx_matrix_open_dev) -------------------------------------------------------------------------
+// The row gather: 2 row_len lanes per opened row, one 16-byte half of an element each, consecutive along the row, so the stores into
+// rows [k][row_len][4] coalesce; the loads are as far apart as the view's element stride puts them.  Element (i, j) of the view is at
+// element index i * row_stride + j * elem_stride (pmx_matrix_shape.hpp: below the view's extent < 2^59 for i < n_rows, j < row_len - the
+// 64-bit products do not wrap).  Device-resident indices are not validated by the host: an index that names no row gets an all-zero
+// row, and nothing outside the view is read.
+__global__ void __launch_bounds__(256) matrix_rows_kernel(const uint4 *__restrict__ matrix, uint64_t n_rows, uint64_t row_len, uint64_t row_stride,
+                                                          uint64_t elem_stride, const uint64_t *__restrict__ indices, uint4 *__restrict__ rows,
+                                                          size_t k) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, per = 2 * (size_t)row_len, i = gid / per;
+    if (i >= k) return;
+    const size_t rest = gid - i * per, j = rest >> 1, half = rest & 1;
+    const uint64_t idx = indices[i];
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (idx < n_rows) v = matrix[(idx * row_stride + j * elem_stride) * 2 + half];
+    rows[gid] = v;
+}
+
 // THE launch of a data-movement kernel, whichever: one lane per 16-byte piece it writes (path_check_kernel: per path), 256 lanes a
 // workgroup, no LDS.  The elements of the callers' uint64_t arrays reach the kernels as their 16-byte halves (u4).
 static const uint4 *u4(const uint64_t *p) { return reinterpret_cast<const uint4 *>(p); }
@@ -156,6 +175,12 @@ hipError_t launch_paths_gather_ragged(const uint64_t *nodes, size_t n_leaves, ui
 hipError_t launch_node_children_bounded(const uint64_t *nodes, const uint64_t *indices, uint64_t pow, uint64_t n_leaves, uint64_t first,
                                         uint64_t width, uint32_t arity, uint64_t *rows, size_t k, hipStream_t st) {
     return plain(node_children_bounded_kernel, k * 2 * arity, st, u4(nodes), indices, pow, n_leaves, first, width, arity, u4(rows), k);
+}
+
+hipError_t launch_matrix_rows(const uint64_t *matrix, size_t n_rows, size_t row_len, size_t row_stride, size_t elem_stride,
+                              const uint64_t *indices, uint64_t *rows, size_t k, hipStream_t st) {
+    return plain(matrix_rows_kernel, k * row_len * 2, st, u4(matrix), (uint64_t)n_rows, (uint64_t)row_len, (uint64_t)row_stride,
+                 (uint64_t)elem_stride, indices, u4(rows), k);
 }
 
 hipError_t launch_node_scatter(const uint64_t *src, const uint64_t *indices, uint64_t pow, uint64_t limit, uint64_t base, uint64_t *dst,

@@ -296,3 +296,81 @@ def verify_rows(parameters: PoseidonConfig, rows: np.ndarray, indices, paths: np
     depth, _ = merkle_ragged_shape(n_rows, arity)
     assert paths.size == idx.shape[0] * depth * (arity - 1) * 4, "paths are [k][depth][arity - 1][4] for the depth of (n_rows, arity)"
     return parameters.context(device).matrix_verify_rows(rows, idx, paths, depth, arity, n_rows, root).astype(bool)
+
+
+def matrix_view_extent(n_rows: int, row_len: int, row_stride: int, elem_stride: int) -> int:
+    """the elements a strided view of a matrix on the device spans, 1 + (n_rows - 1) * row_stride + (row_len - 1) * elem_stride
+    (pmx_matrix_view_extent: host only; an empty dimension, a zero stride or a byte size beyond size_t is a PmxError)"""
+    extent = ctypes.c_size_t()
+    _lib.check(_lib.lib().pmx_matrix_view_extent(n_rows, row_len, row_stride, elem_stride, ctypes.byref(extent)))
+    return extent.value
+
+
+class DeviceMatrixCommitment:
+    """MatrixCommitment for a matrix that already lives on the device (include/poseidon_mi355x_resident.h): `ptr` is a raw device address
+    and the matrix a strided view of it, element (i, j) at ptr + (i * row_stride + j * elem_stride) * 32 bytes - (1, ld) column-major as
+    an NTT leaves it, (row_len, 1) row-major, a block of a larger matrix.  Nothing is copied or transposed, and nothing comes to the
+    host: the constructor enqueues pmx_matrix_commit_dev on `stream` (None: the default stream) into a node array this object owns
+    (pmx_device_alloc), `.root_ptr` is the device address of the root, `.open` and `.verify_rows_dev` enqueue on the same stream.
+    No torch here: a caller that holds its memory in torch tensors passes data_ptr() and torch.cuda.current_stream().cuda_stream.
+    `.close()` frees what the object allocated (the node array and what open() handed out) once the stream's work is done."""
+
+    def __init__(self, parameters: PoseidonConfig, ptr: int, n_rows: int, row_len: int, row_stride: int, elem_stride: int, arity: int = 2,
+                 stream=None, device: int = 0):
+        self.parameters, self.device, self.stream = parameters, device, stream
+        self.ptr, self.n_rows, self.row_len, self.row_stride, self.elem_stride, self.arity = ptr, n_rows, row_len, row_stride, elem_stride, arity
+        self.extent = matrix_view_extent(n_rows, row_len, row_stride, elem_stride)
+        self.depth, self.n_nodes = merkle_ragged_shape(n_rows, arity)
+        self._blocks: List[ctypes.c_void_p] = []
+        self.nodes_ptr = self._alloc(self.n_nodes * 32)
+        try:
+            self._ctx().matrix_commit_dev(ptr, n_rows, row_len, row_stride, elem_stride, arity, self.nodes_ptr, stream)
+        except _lib.PmxError:
+            self.close()
+            raise
+
+    def _ctx(self):
+        return self.parameters.context(self.device)
+
+    def _alloc(self, nbytes: int) -> int:
+        d = ctypes.c_void_p()
+        _lib.check(_lib.lib().pmx_device_alloc(self.device, ctypes.byref(d), max(nbytes, 32)))
+        self._blocks.append(d)
+        return d.value
+
+    @property
+    def root_ptr(self) -> int:
+        """device address of the root [4]: the last row of the node array"""
+        return self.nodes_ptr + (self.n_nodes - 1) * 32
+
+    def open(self, d_indices_ptr: int, k: int, with_paths: bool = True):
+        """(d_rows, d_paths): device addresses of the k opened rows [k][row_len][4] and of their paths [k][depth][arity - 1][4] (None
+        without paths) for the k u64 indices at d_indices_ptr, which never leave the device (pmx_matrix_open_dev).  An index >= n_rows
+        gets an all-zero row and path.  The blocks belong to this object."""
+        d_rows = self._alloc(k * self.row_len * 32)
+        d_paths = self._alloc(k * self.depth * (self.arity - 1) * 32) if with_paths else None
+        self._ctx().matrix_open_dev(self.ptr, self.n_rows, self.row_len, self.row_stride, self.elem_stride,
+                                    self.nodes_ptr if with_paths else None, self.arity, d_indices_ptr, k, d_rows, d_paths, self.stream)
+        return d_rows, d_paths
+
+    def verify_rows_dev(self, d_rows: int, d_indices_ptr: int, d_paths: int, k: int, d_ok: int, d_root: int = None, d_work: int = None) -> None:
+        """d_ok[i] = 1 iff opened row i climbs its path to the root (this commitment's unless d_root is given) and its index is below
+        n_rows (pmx_matrix_verify_rows_dev).  d_work: [k][(arity + 2) * 4] u64 of scratch, allocated here when not given."""
+        if d_work is None:
+            d_work = self._alloc(k * (self.arity + 2) * 32)
+        self._ctx().matrix_verify_rows_dev(d_rows, self.row_len, d_indices_ptr, d_paths, self.depth, self.arity, self.n_rows, k,
+                                           self.root_ptr if d_root is None else d_root, d_ok, d_work, self.stream)
+
+    def close(self) -> None:
+        L = _lib.lib()
+        if self._blocks:
+            L.pmx_stream_synchronize(self.device, self.stream)
+        for d in self._blocks:
+            L.pmx_device_free(self.device, d)
+        self._blocks = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -567,6 +567,28 @@ class Context:
     def merkle_2to1_dev(self, d_nodes: int, n_leaves: int, stream: int = 0) -> None:
         _lib.check(_lib.lib().pmx_merkle_2to1_dev(self._h, d_nodes, n_leaves, stream))
 
+    # ---- matrix commitments on a matrix that lives on the device (include/poseidon_mi355x_resident.h) ---
+    # The matrix is a strided view: element (i, j) at d_matrix + (i * row_stride + j * elem_stride) * 32 bytes.
+    def matrix_leaves_dev(self, d_matrix: int, n_rows: int, row_len: int, row_stride: int, elem_stride: int, d_leaves: int, stream: int = 0) -> None:
+        _lib.check(_lib.lib().pmx_matrix_leaves_dev(self._h, d_matrix, n_rows, row_len, row_stride, elem_stride, d_leaves, stream))
+
+    def matrix_commit_dev(self, d_matrix: int, n_rows: int, row_len: int, row_stride: int, elem_stride: int, arity: int, d_nodes: int,
+                          stream: int = 0) -> None:
+        """d_nodes: [n_nodes][4] of merkle_ragged_shape(n_rows, arity); the digests land in its first n_rows rows, the root is its last"""
+        _lib.check(_lib.lib().pmx_matrix_commit_dev(self._h, d_matrix, n_rows, row_len, row_stride, elem_stride, arity, d_nodes, stream))
+
+    def matrix_open_dev(self, d_matrix: int, n_rows: int, row_len: int, row_stride: int, elem_stride: int, d_nodes, arity: int, d_indices: int,
+                        k: int, d_rows: int, d_paths, stream: int = 0) -> None:
+        """d_rows [k][row_len][4]; d_paths [k][depth][arity - 1][4] out of d_nodes, or both None: rows only.  An index >= n_rows gets zeros."""
+        _lib.check(_lib.lib().pmx_matrix_open_dev(self._h, d_matrix, n_rows, row_len, row_stride, elem_stride, d_nodes, arity, d_indices, k,
+                                                  d_rows, d_paths, stream))
+
+    def matrix_verify_rows_dev(self, d_rows: int, row_len: int, d_indices: int, d_paths, depth: int, arity: int, n_rows: int, k: int, d_root: int,
+                               d_ok: int, d_work: int, stream: int = 0) -> None:
+        """d_work: [k][(arity + 2) * 4] u64 of scratch; d_ok: k bytes at any address."""
+        _lib.check(_lib.lib().pmx_matrix_verify_rows_dev(self._h, d_rows, row_len, d_indices, d_paths, depth, arity, n_rows, k, d_root, d_ok,
+                                                         d_work, stream))
+
 
 # ---------------------------------------------------------------------------------------------------
 # Sponges
